@@ -1,6 +1,12 @@
 """Benchmark of the CPN inference hot path on MI355X: tiles/sec for 3x512x512 tiles with CpnResNeXt101UNet.
 
-    python bench.py --gpus N --steps K --warmup W [--workload tiles|slide]
+    python bench.py --gpus N --steps K --warmup W [--workload tiles|slide] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, and the roofline
+figures the timed steps' own HIP events give).  ``--full`` adds everything else the line used to carry, each outside the
+headline's timed region: the per-op-timed roofline parts (backbone stack, dominant kernel), the shader-clock probe, the
+synchronous and score-gated rates, the other BASELINE configurations, the CPU baseline and the parity numbers against the
+oracle.  ``--dump-outputs DIR`` writes what the timed path returned in its last step as DIR/<name>.npy (rank 0).
 
 ``--gpus N`` with N > 1 and no torchrun environment re-launches itself as
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` (one rank per GPU, RCCL);
@@ -47,6 +53,41 @@ TRAFFIC_FILE = os.path.join(ROOT, 'profiles', 'traffic.json')  # written by tool
 
 
 CALIB_RECIPE = 'shift-4.5_gain3_f1.5_l.5_v1'  # part of the cache key of the calibrated synthetic weights
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(y, out_dir, seed=0):
+    """--dump-outputs: the arrays a caller of the timed path received in its last step, as <out_dir>/<key>.npy.  Floating
+    outputs are written as float32 (float64 ones as float64), integer ones (classes, per-image counts) as float64, which holds
+    them exactly.  Per-image lists (the tile workload's forward() output) are concatenated along the detection axis and
+    `detections_per_image.npy` holds their lengths.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the detection
+    rows is kept, the same rows of every array, and `rows_kept.npy` holds their indices.  -> {name: shape}"""
+    import numpy as np
+    arrays, counts = {}, None
+    for k, v in y.items():
+        if v is None:
+            continue
+        if isinstance(v, (list, tuple)):
+            counts = [int(t.shape[0]) for t in v]
+            v = torch.cat(list(v)) if v else torch.zeros(0)
+        v = v.detach().cpu()
+        arrays[k] = v.numpy().astype(np.float64) if v.dtype == torch.float64 or not v.is_floating_point() else v.float().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    rows = {a.shape[0] for a in arrays.values() if a.ndim}
+    if total > DUMP_LIMIT_BYTES and len(rows) == 1:
+        n = rows.pop()
+        per_row = total / n + 8  # (+ its index in rows_kept)
+        keep = np.sort(np.random.default_rng(seed).choice(n, int(DUMP_LIMIT_BYTES * 0.99 / per_row), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays['rows_kept'] = keep.astype(np.float64)
+    elif total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs: {total} bytes of outputs with different row counts {sorted(rows)}')
+    if counts is not None:
+        arrays['detections_per_image'] = np.asarray(counts, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 PHASES = {'import_torch': time.perf_counter() - _T_PROCESS}
@@ -588,7 +629,7 @@ def main():
     ap.add_argument('--stride', type=int, default=384, help='tile stride of the slide workload')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help="'nccl' = RCCL; 'gloo' only with --dry-run")
     ap.add_argument('--dry-run', action='store_true', help='CPU plumbing check of launch + sharding + gather (no GPU)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the parity numbers')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp8'],
                     help="conv-graph precision; 'fp8' (e4m3, K=64 scaled MFMA) is BASELINE.json configs[4] groundwork, "
                          'the headline metric is quoted on bf16')
@@ -600,7 +641,13 @@ def main():
     ap.add_argument('--sparse-heads', action='store_true',
                     help='score-gated location / Fourier heads -- evaluated at the proposal pixels only, identical outputs '
                          '(csrc/sparse_heads.hip); bf16 only.  The default line stays the dense reference graph')
-    ap.add_argument('--no-extras', action='store_true', help='skip the sync_forward / gated sub-measurements (profiling runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-op roofline profile, shader clock, sync_forward / gated / configs lines, '
+                         'CPU baseline and parity vs the oracle (all outside the timed region)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned in its last step as DIR/<name>.npy (rank 0; float32 / float64, '
+                         'at most 64 MB)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the sync_forward / gated sub-measurements')
     ap.add_argument('--no-subpixel', action='store_true',
                     help='A/B switch: run the UNet decoder convs over upsampled maps as the reference states them instead '
                          'of their sub-pixel decomposition (model.subpixel = False)')
@@ -734,9 +781,12 @@ def main():
     dt, ev, y = timed(args.steps, args.warmup, args.pipeline)
     mem1 = torch.cuda.memory_stats(dev).get('num_device_alloc', 0)
     phase('timed_region')
-    sclk = _sclk_mhz(dev)  # right after the timed region, per rank
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(y, args.dump_outputs)
+        print(f'bench.py: outputs of the last timed step -> {args.dump_outputs}: {shapes}', file=sys.stderr)
+    sclk = _sclk_mhz(dev) if args.full else None  # right after the timed region, per rank
     setup_ranks = setup_per_rank(dev, world, dist)
-    if dist:
+    if dist and args.full:
         t = torch.tensor([sclk if sclk is not None else -1.], dtype=torch.float64, device=dev)
         allc = [torch.zeros_like(t) for _ in range(world)]
         td.all_gather(allc, t)
@@ -753,7 +803,7 @@ def main():
     dominant = None
     prof = None
     prof_batch = args.batch
-    if rank == 0:
+    if rank == 0 and (args.full or args.profile_layers):
         from celldetection_amd.graph import reference_flops
         peng = eng
         if eng.sparse:  # per-op timing needs a plan whose heads all run inside the graph: profile the dense plan's ops
@@ -834,7 +884,8 @@ def main():
         ndet = sum(len(s) for s in y['scores'])
         # conv launches of one graph execution (sub-pixel triples run either their head or their two member ops: per-op
         # executed FLOPs of the profiled run tell which)
-        n_launch = sum(1 for p in prof if p['op'] in ('conv', 'conv_pair', 'conv_bridge') and p['gflop'] > 0) - (2 if args.sparse_heads and eng.sparse else 0)
+        n_launch = None if prof is None else \
+            sum(1 for p in prof if p['op'] in ('conv', 'conv_pair', 'conv_bridge') and p['gflop'] > 0) - (2 if args.sparse_heads and eng.sparse else 0)
         rccl_world = td.get_world_size() if dist else None  # None: no process group exists (one rank, RCCL never initialised)
         assert rccl_world is None or rccl_world == world == args.gpus, (rccl_world, world, args.gpus)
         gated = None
@@ -857,7 +908,7 @@ def main():
                                       == ('CpnResNeXt101UNet', 16, 512, 'bf16') else '')
                                    + ', synthetic weights of the reference shapes',
                        'tiles_per_gpu_per_step': args.batch, 'detections_last_step': ndet,
-                       'world_size_seen_by_rccl': rccl_world, 'sclk_mhz_per_rank_after_timing': sclk_all,
+                       'world_size_seen_by_rccl': rccl_world,
                        'parity_statement': 'bf16 conv graph: matched against the fp32 reference (gates = 2 x the measured error, '
                                            'tests/golden/bf16_measured.json); decode / NMS bit-exact on identical head maps; '
                                            'precision=fp32 reproduces the reference within 1e-4; `parity` = numbers measured in this run',
@@ -868,8 +919,9 @@ def main():
                                 'HIP-event bracket of the conv graph)' if args.sparse_heads else 'dense (reference graph)'},
             'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': achieved / peak,
                          'traffic': traffic if not (args.sparse_heads or args.no_subpixel) else None, 'traffic_source': traffic_src,
-                         'kernel': f'conv_igemm_kernel: one conv-graph execution = {n_launch} launches of the kernel family '
-                                   '(+ input/maxpool helpers), timed with HIP events on the launch stream',
+                         'kernel': 'conv_igemm_kernel: one conv-graph execution = '
+                                   + (f'{n_launch} launches of the kernel family ' if n_launch is not None else 'the kernel family ')
+                                   + '(+ input/maxpool helpers), timed with HIP events on the launch stream',
                          'launch_ms': conv_ms, 'algorithmic_gflop_per_launch': gf * args.batch,
                          'executed_gflop_per_launch': executed, 'executed_frac': executed / conv_ms / peak,
                          'backbone_stack': backbone, 'dominant_kernel': dominant,
@@ -886,6 +938,8 @@ def main():
                              'random_operands': 0.677 if args.precision == 'fp8' else 0.615,
                              'source': 'profiles/r06_kernel_experiments.txt #14 (tools/probes/mfma_lds_ratio.hip)'}},
         }
+        if args.full:
+            out['config']['sclk_mhz_per_rank_after_timing'] = sclk_all
         if gated is not None:
             step_ms = 1e3 * dt / args.steps
             ex = executed + gated['sparse_kernel_gflop']
@@ -898,7 +952,7 @@ def main():
                               'HIP-event bracket of the conv graph',
                 'executed_gflop_per_step': ex, 'sparse_kernel_gflop_per_step': gated['sparse_kernel_gflop'],
                 'algorithmic_frac': gf * args.batch / step_ms / peak})
-        if world == 1 and args.precision == 'bf16' and not args.sparse_heads and not args.no_extras:
+        if args.full and world == 1 and args.precision == 'bf16' and not args.sparse_heads and not args.no_extras:
             # ---- same run, same box, outside the headline's timed region
             steps2 = max(5, args.steps // 2)
             if args.pipeline:  # the rate a caller of forward() per batch gets (LitCpn._predict_step, model(x)): no overlap of
@@ -923,7 +977,7 @@ def main():
                     out.setdefault('configs', {'lines': []})['error'] = f'{type(e).__name__}: {e}'
                     torch.cuda.empty_cache()
                 phase('configs')
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out['cpu_baseline'] = cpu_baseline(sd, args.tile)
             except Exception as e:  # (the contract asks for the object: say why it is missing rather than lose the line)
@@ -1131,10 +1185,13 @@ def slide_workload(args, model, dev, world, rank, dist):
         dt, t_tiles, t_gather, t_nms = (float(v) for v in tt.tolist())
     else:
         t_tiles, t_gather, t_nms = (sum(t[k] for t in tim) for k in ('tiles', 'gather', 'nms'))
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(res, args.dump_outputs)
+        print(f'bench.py: outputs of the last timed step -> {args.dump_outputs}: {shapes}', file=sys.stderr)
     # the product default (sparse_heads = 'auto': score-gated location / Fourier heads, identical detections) over the same
     # slide, every rank, outside the headline's timed region
     gated = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         model.sparse_heads = 'auto'
         inference.tiled_inference(model, slide[:, :edge, :edge], **kw)  # (packs the gated plan, captures its graphs)
         inference.tiled_inference(model, warm, **kw)

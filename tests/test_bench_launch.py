@@ -82,3 +82,30 @@ def test_host_threads_follow_the_cpu_quota(monkeypatch):
     assert [bench.host_threads(w) for w in (1, 2, 4, 8, 32)] == [16, 8, 4, 2, 1]
     monkeypatch.setattr(bench, '_cpu_quota', lambda: None)
     assert bench.host_threads(8) == 32
+
+
+def test_dump_outputs_writes_what_the_caller_received(tmp_path, monkeypatch):
+    """--dump-outputs: per-image lists are concatenated (counts in detections_per_image.npy), floats stay float32, integers
+    become float64, and above the size cap the same seeded rows of every array are kept."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    y = {'contours': [torch.rand(5, 8, 2, generator=g), torch.rand(0, 8, 2)],
+         'scores': [torch.rand(5, generator=g), torch.rand(0)],
+         'classes': [torch.ones(5, dtype=torch.int64), torch.ones(0, dtype=torch.int64)], 'box_uncertainties': None}
+    shapes = bench.dump_outputs(y, str(tmp_path / 'a'))
+    assert shapes == {'contours': [5, 8, 2], 'scores': [5], 'classes': [5], 'detections_per_image': [2]}
+    c = np.load(tmp_path / 'a' / 'contours.npy')
+    assert c.dtype == np.float32 and np.array_equal(c, y['contours'][0].numpy())
+    assert np.load(tmp_path / 'a' / 'classes.npy').dtype == np.float64
+    assert np.load(tmp_path / 'a' / 'detections_per_image.npy').tolist() == [5., 0.]
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 1000)
+    big = {'boxes': torch.rand(200, 4, generator=g), 'b': torch.arange(200, dtype=torch.int32)}
+    for d in ('b1', 'b2'):
+        bench.dump_outputs(big, str(tmp_path / d))
+    keep = np.load(tmp_path / 'b1' / 'rows_kept.npy')
+    assert np.array_equal(keep, np.load(tmp_path / 'b2' / 'rows_kept.npy')) and 0 < len(keep) < 200
+    assert np.array_equal(np.load(tmp_path / 'b1' / 'b.npy'), keep)
+    assert sum(os.path.getsize(tmp_path / 'b1' / f) for f in ('boxes.npy', 'b.npy', 'rows_kept.npy')) < 1000 + 3 * 128  # (+ headers)

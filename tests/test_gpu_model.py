@@ -809,7 +809,7 @@ def test_full_size_properties_config1_resnet18fpn(dev):
     north_star_check('configs[1] tile 0, after NMS', model(x[:1], nms=True), ref_nms)
 
 
-def test_full_width_cpnu22_config0(dev):
+def test_full_width_cpnu22_config0(dev, monkeypatch):
     """BASELINE.json configs[0] on the HIP path: the FULL-WIDTH ``CpnU22(3)`` (31.6 M parameters, base_channels 64) on one
     3x256x256 tile -- bf16 (the product precision) IoU-matched against the fp32 CPU oracle, then the north-star statement on
     the fp32 verification path, and the default-init model (0 detections) through the whole path."""
@@ -818,6 +818,9 @@ def test_full_width_cpnu22_config0(dev):
     import celldetection_amd as cda
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from bench import build_model
+    # no committed calibration for this model / tile (tools/bench_calibration/): calibrate in-process rather than read or
+    # write a cache file outside the repository
+    monkeypatch.setenv('CPN_BENCH_CACHE', '0')
     model, sd = build_model('CpnU22', dev, tile=256)
     assert sum(v.numel() for k, v in model.state_dict().items() if 'num_batches' not in k and 'running' not in k
                and k != 'order_weights') > 31e6
