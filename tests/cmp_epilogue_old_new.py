@@ -22,7 +22,7 @@ if len(sys.argv)>1:
     from test_gpu_kernels import run_conv
     outs=[]
     for c in CASES:
-        got,ref,f32=run_conv(torch.device('cuda:0'),**c); outs.append((got,ref))
+        got,chk,f32=run_conv(torch.device("cuda:0"),**c); outs.append((got,chk.ref.float()))
     torch.save(outs, sys.argv[1]); sys.exit(0)
 res={}
 for tag,lib in (('new',None),('old',os.path.join(ROOT,'celldetection_amd/build/variants/libcpn_oldepi.so'))):

@@ -1,6 +1,7 @@
-"""Seeded random shapes through the single-conv entry point (cpn_conv2d) against the fp32 conv of the same bf16-rounded operands --
-the checker and tolerances of tests/test_gpu_kernels.py::test_conv, on shapes nobody wrote down: ragged tiles, odd channel counts,
-two sources with / without the x2 nearest upsample, residuals, strides, groups, fused ReadOut tails, bilinear sources, narrow maps.
+"""Seeded random shapes through the single-conv entry point (cpn_conv2d) against the fp64 conv of the same operands -- the
+rounding-bound checker of tests/test_gpu_kernels.py::test_conv (tests/conv_bounds.py, guard bands and padded channels included),
+on shapes nobody wrote down: ragged tiles, odd channel counts, two sources with / without the nearest upsample (odd sizes too),
+residuals, strides, groups, fused ReadOut tails, bilinear sources, narrow maps.  Every exception counts as a failure.
 
     python tests/fuzz_conv.py [cases] [seed]        prints one line per failure and a summary; exit code 1 if anything failed
 """
@@ -14,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))  # (this file lives there: run_conv is the kernel tests' helper)
 from test_gpu_kernels import run_conv  # noqa: E402
+import conv_bounds as cb  # noqa: E402
 
 
 def sample(rng):
@@ -64,26 +66,29 @@ def sample(rng):
         cfg['bn'] = False
         cfg['act'] = rng.choice(['none', 'sigmoid', 'tanh_scaled'])
         cfg['out_f32'] = True
-    if cfg.get('up0') or cfg.get('up1') or cfg.get('res_up') or cfg.get('bilinear'):
+    if cfg.get('bilinear'):  # (MODE_BL's blend weights are exact only at x2; nearest sources take odd sizes)
         cfg['h'] += cfg['h'] % 2
         cfg['w'] += cfg['w'] % 2
+    elif cfg.get('up0') or cfg.get('up1') or cfg.get('res_up'):
+        # odd sizes from an RNG of the case's own: the main sequence (and the cases of the recorded runs) stays as it was
+        odd = random.Random(cfg['seed'])
+        if odd.random() < .5:
+            cfg['h'] += odd.choice([-1, 1])
+            cfg['w'] += odd.choice([-1, 1])
     return kind, cfg
 
 
 def check(name, cfg):
-    got, ref, f32 = run_conv(torch.device('cuda:0'), **cfg)
-    if got.shape != ref.shape or not torch.isfinite(got).all():
-        return f'shape {tuple(got.shape)} vs {tuple(ref.shape)}, non-finite {(~torch.isfinite(got)).sum().item()}'
-    err = (got - ref).abs()
-    scale = ref.abs().max().item() + 1e-6
-    tol = (2e-3 if f32 else 1e-2) * max(scale, 1.)
-    bad = (err > tol + (0 if f32 else 8e-3) * ref.abs()).sum().item()
-    # fused tails round the hidden activation to bf16: a value on a rounding boundary may round the other way than in the reference,
-    # and ONE flipped hidden unit moves all fuse_cout outputs of its pixel (tanh_scaled x 3 on top)
-    allowed = max(int(cfg['fuse_cout']), int(2e-4 * err.numel())) if cfg.get('fuse_cout') else 0
-    if bad > allowed or (allowed and err.max().item() >= 5e-2 * max(scale, 1.)):
-        return f'{bad} / {err.numel()} elements off; max abs err {err.max().item():.4e}, ref max {scale:.3e}'
+    """None, or what is wrong; the largest |got - ref| / bound of the passing cases goes to WORST."""
+    got, chk, f32 = run_conv(torch.device('cuda:0'), **cfg)
+    try:
+        WORST[0] = max(WORST[0], chk(name, got))
+    except AssertionError as e:
+        return str(e)
     return None
+
+
+WORST = [0.]
 
 
 def sample_fp8(rng):
@@ -124,9 +129,11 @@ def run_fp8(cases=100, seed=0):
             tk.test_conv_fp8_vs_dequantised_reference(dev, '_fuzz')
         except Exception as e:
             failed += 1
-            print(f'[{i}] fp8 {kind} FAILED {type(e).__name__}: {str(e)[:200]}  {cfg}', flush=True)
+            print(f'[{i}] fp8 {kind} FAILED {type(e).__name__}: {str(e)[:400]}  {cfg}', flush=True)
     tk.FP8_CASES.pop('_fuzz', None)
-    print(f'fuzz_conv (e4m3): {cases} cases {kinds}, {failed} failed')
+    blk = max(tk.FP8_BLOCK_ERR, default=0.)
+    print(f'fuzz_conv (e4m3): {cases} cases {kinds}, {failed} failed; e4m3 block sum error max |got - ref| / S = {blk:.3e} '
+          f'over {len(tk.FP8_BLOCK_ERR)} fp32-output cases (model: {cb.E4M3_BLOCK_U:.3e})')
     return failed
 
 
@@ -138,15 +145,15 @@ def run(cases=200, seed=0):
         kinds[kind] = kinds.get(kind, 0) + 1
         try:
             msg = check(kind, cfg)
-        except Exception as e:  # a shape the plan / launcher rejects is reported, not counted as a numerical failure
+        except Exception as e:  # a launch error, a rejected shape, a touched guard band: all count
             errors += 1
-            print(f'[{i}] {kind} REJECTED {type(e).__name__}: {str(e)[:160]}  {cfg}', flush=True)
+            print(f'[{i}] {kind} ERROR {type(e).__name__}: {str(e)[:400]}  {cfg}', flush=True)
             continue
         if msg:
             failed += 1
-            print(f'[{i}] {kind} FAILED {msg}  {cfg}', flush=True)
-    print(f'fuzz_conv: {cases} cases {kinds}, {failed} failed, {errors} rejected')
-    return failed
+            print(f'[{i}] {kind} FAILED {msg[:400]}  {cfg}', flush=True)
+    print(f'fuzz_conv: {cases} cases {kinds}, {failed} failed, {errors} errors; max |got - ref| / bound {WORST[0]:.3g}')
+    return failed + errors
 
 
 if __name__ == '__main__':

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bounds as cb
+
 pytestmark = pytest.mark.gpu
 
 
@@ -64,6 +66,7 @@ def test_conv_bridge_kernel(dev, name, brf, monkeypatch):
     """Both tiles of the fused kernel: MODE_BR (default: the <16,64,2,2> tile) and MODE_BRF (CPN_BRF=1: 8-row tiles on 4 waves,
     flat pitch-34 halo tiles, two workgroups per CU -- measured neutral, kept as an opt-in)."""
     from celldetection_amd import _lib, graph
+    from celldetection_amd.subpixel import collapse_upsampled_taps, phase_padding
     monkeypatch.setenv('CPN_BRF', brf)
     cfg = dict(seed=0)
     cfg.update(CASES[name])
@@ -77,30 +80,38 @@ def test_conv_bridge_kernel(dev, name, brf, monkeypatch):
     d0[..., :cin] = x.permute(0, 2, 3, 1).to(torch.bfloat16).to(dev)
     lib = _lib.load()
     H, W = 2 * h, 2 * w
-    fused = torch.full((n, H, W, 64), float('nan'), dtype=torch.bfloat16, device=dev)
+    fused, fbuf, fg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
     _lib.check(lib.cpn_conv_bridge(ops[2], _lib.ptr(d0), cs, None, 0, _lib.ptr(fused), 64, n, h, w, _lib.ptr(wblob),
                                    _lib.ptr(bblob), _lib.stream_ptr()), 'conv_bridge')
-    mid = torch.full((n, H, W, 64), float('nan'), dtype=torch.bfloat16, device=dev)
-    two = torch.full((n, H, W, 64), float('nan'), dtype=torch.bfloat16, device=dev)
+    mid, mbuf, mg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
+    two, tbuf, tg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
     # the scattered phase conv takes the LOW-resolution size, the 3x3 conv the full-resolution one
     _lib.check(lib.cpn_conv2d(ops[0], _lib.ptr(d0), cs, None, 0, None, 0, _lib.ptr(mid), 64, n, h, w, _lib.ptr(wblob),
                               _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d scatter')
     _lib.check(lib.cpn_conv2d(ops[1], _lib.ptr(mid), 64, None, 0, None, 0, _lib.ptr(two), 64, n, H, W, _lib.ptr(wblob),
                               _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d 3x3')
     torch.cuda.synchronize()
-    assert torch.isfinite(fused.float()).all()
-    assert torch.equal(fused, two), f'{name}: fused bridge differs from the two launches: max abs ' \
-                                    f'{(fused.float() - two.float()).abs().max().item():.3e}, ' \
-                                    f'{(fused != two).float().mean().item():.2e} of the outputs'
-    # the reference's statement of the level, fp32 on the bf16-rounded input (the sub-pixel form rounds the collapsed tap sums once:
-    # the usual tolerance)
+    got = cb.assert_nhwc_bf16('conv_bridge', fbuf, fg, fused, 64)
+    got_mid = cb.assert_nhwc_bf16('scatter launch', mbuf, mg, mid, 64)
+    got_two = cb.assert_nhwc_bf16('3x3 launch', tbuf, tg, two, 64)
+    assert torch.equal(got, got_two), f'{name}: fused bridge differs from the two launches: max abs ' \
+                                      f'{(got - got_two).abs().max().item():.3e}, {(got != got_two).float().mean().item():.2e} of the outputs'
+    # each of the two launches against the fp64 conv of what it read: the four 2x2 phase convs (collapsed taps, rounded to
+    # bf16 by the packer) of the low-resolution input, then the 3x3 conv of the intermediate the first launch stored
     w1, b1 = graph._fold(sd, P.ops[0])
     w2, b2 = graph._fold(sd, P.ops[1])
-    r = F.relu(F.conv2d(F.interpolate(x, scale_factor=2, mode='nearest'), w1.float(), b1.float(), 1, 1)).to(torch.bfloat16).float()
-    ref = F.relu(F.conv2d(r, w2.float().to(torch.bfloat16).float(), b2.float(), 1, 1))
-    got = fused.float().permute(0, 3, 1, 2).cpu()
-    scale = max(ref.abs().max().item(), 1.)
-    assert (got - ref).abs().max().item() < 5e-2 * scale, (got - ref).abs().max().item()
+    wc = collapse_upsampled_taps(w1).to(torch.bfloat16).double()
+    ref1, S1 = torch.zeros(n, 64, H, W, dtype=torch.float64), torch.zeros(n, 64, H, W, dtype=torch.float64)
+    for py in (0, 1):
+        for px in (0, 1):
+            pt, pl = phase_padding(py), phase_padding(px)
+            ref1[:, :, py::2, px::2], S1[:, :, py::2, px::2] = cb.conv64(F.pad(x.double(), (pl, 1 - pl, pt, 1 - pt)), wc[py, px],
+                                                                         b1.to(torch.float32))
+    d1 = cb.gamma(cb.chain_length(2, 2, cs)) * S1
+    r1 = cb.check(f'{name} scatter', got_mid, *cb.bf16_bounds(ref1, d1, 'relu'), F.relu(ref1), S1)
+    ref2, S2, d2 = cb.conv_with_noise(got_mid, w2.to(torch.bfloat16), b2.to(torch.float32), 1, 1, n=cb.chain_length(3, 3, 64))
+    r2 = cb.check(f'{name} 3x3', got_two, *cb.bf16_bounds(ref2, d2, 'relu'), F.relu(ref2), S2)
+    print(f'{name}: max |got - ref| / bound: scatter {r1:.3g}, 3x3 {r2:.3g}')
 
 
 def test_conv_bridge_in_the_plan_and_switch(dev, monkeypatch):

@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bounds as cb
+
 pytestmark = pytest.mark.gpu
 
 
@@ -59,21 +61,27 @@ def run_pair(dev, *, n, h, w, cin, cmid, groups=32, seed=0, stride=1):
     d0[..., :cin] = x.permute(0, 2, 3, 1).to(torch.bfloat16).to(dev)
     lib = _lib.load()
     cm = _pad32(cmid)
-    fused = torch.full((n, ho, wo, cm), float('nan'), dtype=torch.bfloat16, device=dev)
+    fused, fbuf, fg = cb.guarded_nhwc_bf16(n, ho, wo, cm, dev)
     _lib.check(lib.cpn_conv_pair(ops[2], _lib.ptr(d0), cs, _lib.ptr(fused), cm, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob),
                                  _lib.stream_ptr()), 'conv_pair')
-    mid = torch.full((n, h, w, cm), float('nan'), dtype=torch.bfloat16, device=dev)
-    two = torch.full((n, ho, wo, cm), float('nan'), dtype=torch.bfloat16, device=dev)
+    mid, mbuf, mg = cb.guarded_nhwc_bf16(n, h, w, cm, dev)
+    two, tbuf, tg = cb.guarded_nhwc_bf16(n, ho, wo, cm, dev)
     for op, src, dst, ss in ((ops[0], d0, mid, cs), (ops[1], mid, two, cm)):
         _lib.check(lib.cpn_conv2d(op, _lib.ptr(src), ss, None, 0, None, 0, _lib.ptr(dst), cm, n, h, w, _lib.ptr(wblob),
                                   _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d')
     torch.cuda.synchronize()
+    got_fused = cb.assert_nhwc_bf16('conv_pair', fbuf, fg, fused, cmid)
+    got_mid = cb.assert_nhwc_bf16('first launch', mbuf, mg, mid, cmid)
+    got_two = cb.assert_nhwc_bf16('second launch', tbuf, tg, two, cmid)
+    # each launch against the fp64 conv of what it read: the 1x1 conv of x, the grouped 3x3 conv of the first launch's output
     w1, b1 = graph._fold(sd, P.ops[0])
     w2, b2 = graph._fold(sd, P.ops[1])
-    r = F.relu(F.conv2d(x, w1.float().to(torch.bfloat16).float(), b1.float())).to(torch.bfloat16).float()
-    ref = F.relu(F.conv2d(r, w2.float().to(torch.bfloat16).float(), b2.float(), stride, 1, 1, groups))
-    nchw = lambda t: t[..., :cmid].permute(0, 3, 1, 2).float().cpu()
-    return nchw(fused), nchw(two), ref
+    ref1, S1, d1 = cb.conv_with_noise(x, w1.to(torch.bfloat16), b1.to(torch.float32), n=cb.chain_length(1, 1, cs))
+    ref2, S2, d2 = cb.conv_with_noise(got_mid, w2.to(torch.bfloat16), b2.to(torch.float32), stride, 1, groups,
+                                      n=cb.chain_length(3, 3, cb.cin_read(cmid, cmid, groups)))
+    checks = [lambda name: cb.check(f'{name} 1x1', got_mid, *cb.bf16_bounds(ref1, d1, 'relu'), F.relu(ref1), S1),
+              lambda name: cb.check(f'{name} 3x3', got_two, *cb.bf16_bounds(ref2, d2, 'relu'), F.relu(ref2), S2)]
+    return got_fused, got_two, checks
 
 
 PAIR_CASES = {
@@ -105,15 +113,12 @@ PAIR_CASES = {
 
 @pytest.mark.parametrize('name', sorted(PAIR_CASES))
 def test_conv_pair(dev, name):
-    fused, two, ref = run_pair(dev, **PAIR_CASES[name])
-    assert torch.isfinite(fused).all()
-    # the two launches it replaces: same operands, K order and rounding points
+    """The fused pair is bit-identical to the two launches it replaces (same operands, K order and rounding points), and each
+    of those launches is within the rounding bound of the fp64 conv of what it read (tests/conv_bounds.py)."""
+    fused, two, checks = run_pair(dev, **PAIR_CASES[name])
     assert torch.equal(fused, two), (name, (fused - two).abs().max().item())
-    err = (fused - ref).abs().max().item()
-    tol = 2e-2 * max(1., ref.abs().max().item())  # bf16 output rounding (2^-8 relative) + fp32 accumulation order
-    rel = ((fused - ref).norm() / (ref.norm() + 1e-12)).item()
-    print(f'{name}: max err {err:.3e} rel L2 {rel:.3e}')
-    assert err <= tol and rel < 5e-3, (name, err, rel)
+    ratios = [c(name) for c in checks]
+    print(f'{name}: max |got - ref| / bound: 1x1 {ratios[0]:.3g}, 3x3 {ratios[1]:.3g}')
 
 
 def test_conv_pair_unsupported_width(dev):
