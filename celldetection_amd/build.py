@@ -27,6 +27,7 @@ SOURCES = {
     'decode_nms.hip': ['-ffp-contract=off'],
     'nms_binned.hip': ['-ffp-contract=off'],
     'labels.hip': [],
+    'instance_eval.hip': [],  # integer only
     'sparse_heads.hip': [],
     'stem.hip': [],
     'cpn_abi.hip': [],

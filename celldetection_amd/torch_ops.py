@@ -80,6 +80,19 @@ def _(boxes, thresh):
     return boxes.new_empty((boxes.shape[0],), dtype=torch.float32)
 
 
+@torch.library.custom_op(f'{NAMESPACE}::label_pair_table', mutates_args=(), device_types='cuda')
+def label_pair_table(inputs: Tensor, targets: Tensor) -> Tensor:
+    """Pixel pass of the instance evaluation (celldetection/data/instance_eval.py:22-50): label images [H, W(, C)] ->
+    int64 [N, 2] rows (key, count), keys ascending; see ``instance_eval.label_pair_table``."""
+    from . import instance_eval
+    return instance_eval.label_pair_table(inputs, targets)
+
+
+@label_pair_table.register_fake
+def _(inputs, targets):
+    return inputs.new_empty((torch.library.get_ctx().new_dynamic_size(), 2), dtype=torch.int64)
+
+
 def install_torchvision_nms(force: bool = False) -> bool:
     """Defines ``torchvision::nms`` (schema of torchvision's operator) with the HIP implementation for GPU tensors when
     torchvision is not installed, so that the reference's ``torch.ops.torchvision.nms(...)`` call sites dispatch to

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 14
+#define CPN_ABI_VERSION 15
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -462,6 +462,38 @@ int cpn_labels_round(const int32_t *points, const int32_t *boxes, int64_t K, int
                      const uint32_t *cell_begin, const uint32_t *cell_end, int32_t *canvas, int32_t channels,
                      uint8_t *state, uint8_t *ready, uint32_t *ready_list, int32_t *channel, int32_t *counters,
                      int32_t *counters_host, int32_t use_ioa, double ioa_thresh, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Instance evaluation of label images (cd.data.LabelMatcher, celldetection/data/instance_eval.py; csrc/instance_eval.hip).
+ * Label images: int32 [pixels][channels] on the device, channel-interleaved, 16-byte aligned; values <= 0 are background;
+ * up to 8 channels per side (CPN_E_UNSUPPORTED above).
+ *   workspace_bytes: bytes for a table of `table_capacity` slots (a power of two) plus the selection state of `pairs`
+ *                    pairs over at most `labels` labels per side; pass 0 for the part a call does not use.
+ *   pairs:           zeroes the table and counts, on the 64-bit key (input << 32 | target): the pixels of every distinct
+ *                    (input label, target label) pair (a pixel counts once per pair), under (label << 32) the elements of
+ *                    every input label and under (label) those of every target label.  Asynchronous.
+ *   table_status:    status_host[0] = inserts that found no slot (> 0: repeat cpn_eval_pairs with a larger table),
+ *                    [1] = occupied slots.  Synchronises the stream.
+ *   compact:         the occupied slots -> keys / counts (int64 [entries], device) in no particular order.
+ *   unions:          for the pairs (sorted keys): position of both labels in the sorted label lists and
+ *                    unions = input count + target count - intersection.  Synchronises the stream.
+ *   select:          greedy one-to-one matching at iou_thresh: pairs with intersection / union (float64) >= iou_thresh, taken
+ *                    from the largest IoU down (exact comparison i1 * u2 vs i2 * u1; equal IoU: lower pair position first)
+ *                    unless one of their labels is taken.  selected: uint8 [pairs]; result_host[0] = pairs taken,
+ *                    [1] = rounds.  Synchronises the stream.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t cpn_eval_workspace_bytes(int64_t table_capacity, int64_t pairs, int64_t labels);
+int cpn_eval_pairs(const int32_t *inputs, int32_t c_in, const int32_t *targets, int32_t c_t, int64_t pixels,
+                   int64_t table_capacity, void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_eval_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream);
+int cpn_eval_compact(void *workspace, int64_t table_capacity, int64_t *keys, int64_t *counts, int64_t entries, void *stream);
+int cpn_eval_unions(const int64_t *pair_keys, const int64_t *intersections, int64_t pairs, const int64_t *input_labels,
+                    const int64_t *input_counts, int64_t n_inputs, const int64_t *target_labels, const int64_t *target_counts,
+                    int64_t n_targets, int64_t *unions, int32_t *input_index, int32_t *target_index, void *workspace,
+                    void *stream);
+int cpn_eval_select(const int64_t *intersections, const int64_t *unions, const int32_t *input_index, const int32_t *target_index,
+                    int64_t pairs, int64_t n_inputs, int64_t n_targets, double iou_thresh, uint8_t *selected, void *workspace,
+                    int64_t workspace_bytes, int64_t *result_host, void *stream);
 
 #ifdef __cplusplus
 }
