@@ -28,6 +28,7 @@ SOURCES = {
     'nms_binned.hip': ['-ffp-contract=off'],
     'labels.hip': [],
     'instance_eval.hip': [],  # integer only
+    'flat_labels.hip': [],  # integer only
     'sparse_heads.hip': [],
     'stem.hip': [],
     'cpn_abi.hip': [],

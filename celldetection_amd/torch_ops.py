@@ -93,6 +93,19 @@ def _(inputs, targets):
     return inputs.new_empty((torch.library.get_ctx().new_dynamic_size(), 2), dtype=torch.int64)
 
 
+@torch.library.custom_op(f'{NAMESPACE}::resolve_label_channels', mutates_args=(), device_types='cuda')
+def resolve_label_channels(labels: Tensor, max_iter: int) -> Tensor:
+    """Flat label image (celldetection/data/cpn.py:361-399, default kernel): label image [H, W, C] -> [H, W]; see
+    ``flat_labels.resolve_label_channels``."""
+    from . import flat_labels
+    return flat_labels.resolve_label_channels(labels, max_iter=max_iter)
+
+
+@resolve_label_channels.register_fake
+def _(labels, max_iter):
+    return labels.new_empty(labels.shape[:2])
+
+
 def install_torchvision_nms(force: bool = False) -> bool:
     """Defines ``torchvision::nms`` (schema of torchvision's operator) with the HIP implementation for GPU tensors when
     torchvision is not installed, so that the reference's ``torch.ops.torchvision.nms(...)`` call sites dispatch to

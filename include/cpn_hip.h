@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 15
+#define CPN_ABI_VERSION 16
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -494,6 +494,35 @@ int cpn_eval_unions(const int64_t *pair_keys, const int64_t *intersections, int6
 int cpn_eval_select(const int64_t *intersections, const int64_t *unions, const int32_t *input_index, const int32_t *target_index,
                     int64_t pairs, int64_t n_inputs, int64_t n_targets, double iou_thresh, uint8_t *selected, void *workspace,
                     int64_t workspace_bytes, int64_t *result_host, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Flat label images (cd.data.resolve_label_channels, celldetection/data/cpn.py:361-399; called from
+ * celldetection_scripts/cpn_inference.py:817; csrc/flat_labels.hip).  labels: int32 [H][W][channels] on the device,
+ * channel-interleaved, 16-byte aligned; lbl: int32 [H][W], 16-byte aligned, the result.  A pixel with more than one
+ * channel > 0 is an overlap pixel, with exactly one a core pixel.  H * W <= 2^31 - 1 (CPN_E_UNSUPPORTED above).
+ * The propagation works on tiles of 32 x 32 pixels; one call of cpn_flat_step runs at most CPN_FLAT_MAX_STEPS steps.
+ * All calls for one image use the same workspace.
+ *   workspace_bytes: counters, a second [H][W] image and the tile flags.
+ *   classify:        plain_max == 0: lbl = channel maximum at core pixels, -1 at overlap pixels (unresolved), 0 elsewhere;
+ *                    marks the tiles that hold overlap pixels.  plain_max != 0: lbl = channel maximum (the result of an
+ *                    image without overlap pixels).  status_host[0] = overlap pixels, [1] = pixels whose maximum is
+ *                    negative (they differ between the two modes).  Synchronises the stream, unless status_host is NULL.
+ *   step:            `steps` (1 .. CPN_FLAT_MAX_STEPS) synchronous steps: every unresolved pixel takes the maximum of lbl over the
+ *                    neighbours named by `footprint` (bit 3 * row + column of a 3 x 3 array anchored at its centre; 0272 is
+ *                    the 4-neighbourhood of cv2.getStructuringElement(MORPH_CROSS, (3, 3))), all pixels at once from the
+ *                    values of the previous step; neighbours outside the image take no part.  `launch` counts the calls for
+ *                    this image from 0: only tiles with unresolved pixels next to a change of the previous call run.
+ *                    status_host[0] = pixels that received a label, [1] = tiles run.  0 pixels: a fixed point.
+ *                    Synchronises the stream, unless status_host is NULL.
+ *   finish:          what is still unresolved becomes 0.  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_FLAT_MAX_STEPS 8
+int64_t cpn_flat_workspace_bytes(int32_t H, int32_t W);
+int cpn_flat_classify(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t plain_max, int32_t *lbl,
+                      void *workspace, int64_t workspace_bytes, int64_t *status_host, void *stream);
+int cpn_flat_step(int32_t *lbl, int32_t H, int32_t W, int32_t steps, int32_t footprint, int32_t launch, void *workspace,
+                  int64_t workspace_bytes, int64_t *status_host, void *stream);
+int cpn_flat_finish(int32_t *lbl, int32_t H, int32_t W, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
