@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
 
@@ -22,6 +22,12 @@ SUBPIXEL_NONE, SUBPIXEL_HEAD, SUBPIXEL_PHASE, SUBPIXEL_LATERAL, SUBPIXEL_SCATTER
 SUBPIXEL_BL_HEAD, SUBPIXEL_BL_PHASE, SUBPIXEL_BL_FRAME = 5, 6, 7
 OUT_SCORES, OUT_LOCATIONS, OUT_FOURIER, OUT_REFINEMENT, OUT_UNCERTAINTY = 0, 1, 2, 3, 4
 NUM_OUTPUTS = 5
+# region properties (CPN_PROP_* of include/cpn_hip.h), in code order, and the intensity dtypes (CPN_PROPS_*)
+PROP_NAMES = ('label', 'bbox', 'num_pixels', 'area', 'area_bbox', 'extent', 'equivalent_diameter_area', 'centroid',
+              'centroid_local', 'inertia_tensor', 'inertia_tensor_eigvals', 'axis_major_length', 'axis_minor_length',
+              'eccentricity', 'orientation', 'intensity_mean', 'intensity_min', 'intensity_max')
+PROP_CODES = {name: code for code, name in enumerate(PROP_NAMES)}
+PROPS_U8, PROPS_I16, PROPS_I32 = 0, 1, 2
 
 
 class TensorDesc(Structure):
@@ -143,6 +149,14 @@ _SIGNATURES = [
     ('cpn_flat_step', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
                                      POINTER(c_int64), c_void_p]),
     ('cpn_flat_finish', ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    ('cpn_props_workspace_bytes', c_int64, [c_int64, c_int32]),
+    ('cpn_props_columns', c_int32, [POINTER(c_int32), c_int32, c_int32]),
+    ('cpn_props_accumulate', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int64, c_void_p,
+                                            c_int64, c_void_p]),
+    ('cpn_props_table_status', ctypes.c_int, [c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    ('cpn_props_compact_sort', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p]),
+    ('cpn_props_finalise', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, POINTER(c_int32), c_int32, c_double, c_double,
+                                          c_void_p, c_int64, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -29,6 +29,8 @@ SOURCES = {
     'labels.hip': [],
     'instance_eval.hip': [],  # integer only
     'flat_labels.hip': [],  # integer only
+    # integer accumulation; the fp64 finalisation is defined by its order of operations: no FMA contraction
+    'region_props.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     'cpn_abi.hip': [],

@@ -106,6 +106,24 @@ def _(labels, max_iter):
     return labels.new_empty(labels.shape[:2])
 
 
+@torch.library.custom_op(f'{NAMESPACE}::region_properties', mutates_args=(), device_types='cuda')
+def region_properties(labels: Tensor, properties: str, spacing_row: float, spacing_col: float) -> Tensor:
+    """Region property table (celldetection/data/misc.py:320-347): label image [H, W(, C)] and comma-separated property names
+    -> float64 [rows, columns], integer columns converted; see ``region_props.region_properties`` for names and order."""
+    from . import region_props
+    cols = region_props.region_properties(labels, tuple(p for p in properties.split(',') if p), spacing=(spacing_row, spacing_col))
+    if not cols:
+        return labels.new_empty((0, 0), dtype=torch.float64)
+    return torch.stack([c.to(torch.float64) for c in cols.values()], 1)
+
+
+@region_properties.register_fake
+def _(labels, properties, spacing_row, spacing_col):
+    from . import region_props
+    names, _ = region_props._column_names(region_props._resolve(tuple(p for p in properties.split(',') if p)), '-', 0)
+    return labels.new_empty((torch.library.get_ctx().new_dynamic_size(), len(names)), dtype=torch.float64)
+
+
 def install_torchvision_nms(force: bool = False) -> bool:
     """Defines ``torchvision::nms`` (schema of torchvision's operator) with the HIP implementation for GPU tensors when
     torchvision is not installed, so that the reference's ``torch.ops.torchvision.nms(...)`` call sites dispatch to

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 16
+#define CPN_ABI_VERSION 17
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -523,6 +523,72 @@ int cpn_flat_classify(const int32_t *labels, int32_t channels, int32_t H, int32_
 int cpn_flat_step(int32_t *lbl, int32_t H, int32_t W, int32_t steps, int32_t footprint, int32_t launch, void *workspace,
                   int64_t workspace_bytes, int64_t *status_host, void *stream);
 int cpn_flat_finish(int32_t *lbl, int32_t H, int32_t W, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Region property tables of label images (cd.data.labels2property_table, celldetection/data/misc.py:320-347, i.e.
+ * skimage.measure.regionprops_table per channel; called from celldetection_scripts/cpn_inference.py:824-837;
+ * csrc/region_props.hip).  ABI 17.
+ * labels: int32 [H][W][channels] on the device, channel-interleaved, 16-byte aligned, channels <= 11; every element v > 0
+ * belongs to the row of (channel, v).  intensity: NULL or an integer image [H][W][intensity_channels] (<= 4 channels) of
+ * dtype CPN_PROPS_U8 / _I16 / _I32.  H * W <= 2^31 - 1 and H, W <= 65536 (CPN_E_UNSUPPORTED above): every sum fits int64.
+ * All accumulation is integer arithmetic, the table is bit-identical from run to run.
+ *   workspace_bytes: counters, a table of `table_capacity` slots (a power of two, <= 2^28) and the sort buffer.
+ *   columns:         number of columns the property list expands to (-1: bad list; host only).
+ *   accumulate:      zeroes the table and reads the image(s) once: per key the pixel count, the sums of r, c, r^2, r * c,
+ *                    c^2 over global pixel coordinates, the bounding box and per intensity channel sum, minimum and
+ *                    maximum.  Asynchronous.
+ *   table_status:    status_host[0] = inserts that found no slot (> 0: repeat accumulate with a larger table),
+ *                    [1] = occupied slots = rows.  Synchronises the stream.
+ *   compact_sort:    orders the occupied slots by (channel, label) ascending inside the workspace.  Asynchronous.
+ *   finalise:        out: int64 [out_columns][entries] on the device with out_columns = columns + 1: one row per column in
+ *                    the order of the property list (vectors and matrices in row-major order, intensity properties one
+ *                    column per intensity channel), float columns as the bit pattern of the fp64 value, and a last row with
+ *                    the channel of each entry.  Asynchronous.
+ * Definitions, with the bounding box r0, c0, r1, c1 (half-open), the spacing (sy, sx) = (spacing_row, spacing_col) and the
+ * sums shifted to the corner of the box in integers (sr = sum r - n * r0, srr = sum r^2 - 2 * r0 * sum r + n * r0^2, ...),
+ * every expression evaluated in fp64 as written, without contraction:
+ *   area = n * (sy * sx); area_bbox = ((r1 - r0) * (c1 - c0)) * (sy * sx); extent = area / area_bbox;
+ *   equivalent_diameter_area = sqrt(4 * area / pi); centroid = ((sum r / n) * sy, (sum c / n) * sx);
+ *   centroid_local = ((sr / n) * sy, (sc / n) * sx);
+ *   mu20 = (srr - sr * sr / n) * (sy * sy); mu02 = (scc - sc * sc / n) * (sx * sx); mu11 = (src - sr * sc / n) * (sy * sx);
+ *   inertia_tensor = [[a, b], [b, c]], a = mu02 / n, b = -mu11 / n, c = mu20 / n;
+ *   inertia_tensor_eigvals = (l1, l2): m = (a + c) / 2, d = (a - c) / 2, s = sqrt(d * d + b * b), l1 = m + s, l2 = max(m - s, 0);
+ *   axis_major_length = 4 * sqrt(l1); axis_minor_length = 4 * sqrt(l2); eccentricity = l1 == 0 ? 0 : sqrt(1 - l2 / l1);
+ *   orientation = a - c == 0 ? (b < 0 ? pi / 4 : -pi / 4) : 0.5 * atan2(-2 * b, c - a);
+ *   intensity_mean = sum i / n; intensity_min, intensity_max.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_PROP_LABEL 0
+#define CPN_PROP_BBOX 1
+#define CPN_PROP_NUM_PIXELS 2
+#define CPN_PROP_AREA 3
+#define CPN_PROP_AREA_BBOX 4
+#define CPN_PROP_EXTENT 5
+#define CPN_PROP_EQUIVALENT_DIAMETER_AREA 6
+#define CPN_PROP_CENTROID 7
+#define CPN_PROP_CENTROID_LOCAL 8
+#define CPN_PROP_INERTIA_TENSOR 9
+#define CPN_PROP_INERTIA_TENSOR_EIGVALS 10
+#define CPN_PROP_AXIS_MAJOR_LENGTH 11
+#define CPN_PROP_AXIS_MINOR_LENGTH 12
+#define CPN_PROP_ECCENTRICITY 13
+#define CPN_PROP_ORIENTATION 14
+#define CPN_PROP_INTENSITY_MEAN 15
+#define CPN_PROP_INTENSITY_MIN 16
+#define CPN_PROP_INTENSITY_MAX 17
+#define CPN_PROP_COUNT 18
+#define CPN_PROPS_U8 0
+#define CPN_PROPS_I16 1
+#define CPN_PROPS_I32 2
+int64_t cpn_props_workspace_bytes(int64_t table_capacity, int32_t intensity_channels);
+int32_t cpn_props_columns(const int32_t *properties, int32_t n_properties, int32_t intensity_channels);
+int cpn_props_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t channels, const void *intensity,
+                         int32_t intensity_channels, int32_t intensity_dtype, int64_t table_capacity, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int cpn_props_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream);
+int cpn_props_compact_sort(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, void *stream);
+int cpn_props_finalise(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries,
+                       const int32_t *properties, int32_t n_properties, double spacing_row, double spacing_col, int64_t *out,
+                       int64_t out_columns, void *stream);
 
 #ifdef __cplusplus
 }
