@@ -21,6 +21,9 @@ from . import _lib, graph, ops
 
 __all__ = ['CPN']
 
+# kernel-selection switches the library reads per launch: a captured hipGraph freezes them, so they are part of its cache key
+GRAPH_KEY_SWITCHES = ('CPN_BLPHASE', 'CPN_PAIR', 'CPN_S1F', 'CPN_S1Q', 'CPN_BRIDGE')
+
 
 class _Container(nn.Module):
     """Anonymous node of the parameter tree (mirrors the reference's module hierarchy for state_dict keys)."""
@@ -307,9 +310,7 @@ class _Engine:
             return cat(0), cat(1), cat(2), cat(3), flag
         slot = None
         if _timed is None and _absmax is None and nb == n and self.precision != 'fp32':
-            # kernel-selection switches that are read per launch are frozen into a captured graph: part of the key
-            env = tuple(os.environ.get(k) for k in ('CPN_RW', 'CPN_PWR', 'CPN_PAIR_CPS', 'CPN_TH64', 'CPN_BLPHASE', 'CPN_PAIR',
-                                                      'CPN_S1F', 'CPN_BRF', 'CPN_S1Q', 'CPN_BRIDGE'))
+            env = tuple(os.environ.get(k) for k in GRAPH_KEY_SWITCHES)
             slot = self._graph_slot((n, x.shape[1], h, w, dt, order_total, bool(refinement), env), x, dt, order_total,
                                     refinement, gated)
         if slot is not None and 'graph' in slot:

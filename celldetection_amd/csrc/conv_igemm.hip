@@ -130,22 +130,10 @@ __device__ __forceinline__ void add_res8(float (&v)[8], const store8_t r, float)
 #endif
 
 // pointwise stride 1 / KxK stride 1 / KxK stride 2 / KxK stride 1 whose source is read through a bilinear resize
-// MODE_S1R = MODE_S1 with the weight operand loaded from L2 straight into registers (dense KxK, >= 9 taps, 8x256 tile)
-// MODE_PWR = MODE_PW with the register-weight loop of MODE_S1R (1x1 convs stream BOTH operands once per output tile: the
-// LDS-DMA issue path is their bottleneck, and the weight half of it moves to plain buffer loads)
 // MODE_N = MODE_S1 for outputs that are exactly 16 pixels wide (the deepest encoder / decoder level of a 512^2 tile): an
 // MFMA pixel fragment is TWO output rows x 16 columns instead of one row x 32, so no half of the 32-pixel tile is empty.
 // [N][H][16] IS [N][H/2][32] in memory, hence the launcher passes the output (and a same-size residual) with those
 // virtual dimensions and the epilogue is unchanged; only the halo geometry and the fragment addresses know about it.
-#ifndef CPN_RW_DEFAULT
-#define CPN_RW_DEFAULT 0  // see conv_mode
-#endif
-#ifndef CPN_S1F_DEFAULT
-#define CPN_S1F_DEFAULT 1  // see flat_ok
-#endif
-#ifndef CPN_WAVE_PRIO
-#define CPN_WAVE_PRIO 1  // alternating wave priority in the e4m3 main loop of the 8-wave tiles (bf16: measured negative)
-#endif
 // MODE_S1F (round 5) = MODE_S1 for TWO co-resident 4-wave workgroups per CU (tile 8 x 32 px x 128 cout, the flagship's 128 px x
 // 64 cout wave tile): a tile's head (first DMA round trip) and tail (LDS-staged epilogue + 64 KiB of stores, MFMA idle) overlap
 // the OTHER workgroup's main loop instead of nothing.  What makes two of them fit the 160 KiB: a FLAT halo tile with a row pitch
@@ -161,12 +149,14 @@ __device__ __forceinline__ void add_res8(float (&v)[8], const store8_t r, float)
 // the bridge level of the ResNet-UNets -- conv 3x3 (64 -> 64, bias-free, BN, ReLU) over the x2-upsampled 64-channel map, run as
 // four 2x2 phase convs (CPN_SUBPIXEL_SCATTER), followed by the second conv 3x3 of that TwoConvNormRelu block -- as ONE launch:
 // the 537 MB full-resolution intermediate of a 16 x 512^2 batch is neither written nor read (ConvArgs.pre_*).
-enum Mode : int { MODE_PW = 0, MODE_S1 = 1, MODE_S2 = 2, MODE_BL = 3, MODE_S1R = 4, MODE_PWR = 5, MODE_N = 6, MODE_S1F = 7, MODE_BR = 8, MODE_BRF = 9, MODE_S1Q = 10 };
+// (The values are part of the mangled kernel names that profiles/ and DESIGN.md quote; 4, 5 and 9 were the register-weight and
+// two-workgroup bridge variants, removed as neutral: profiles/r06_pw_register_weights.txt, r05_kernel_experiments.txt #6.)
+enum Mode : int { MODE_PW = 0, MODE_S1 = 1, MODE_S2 = 2, MODE_BL = 3, MODE_N = 6, MODE_S1F = 7, MODE_BR = 8, MODE_S1Q = 10 };
 
 template <int MODE>
 struct ModeCfg {
     static constexpr int S = MODE == MODE_S2 ? 2 : 1;                              // conv stride
-    static constexpr int PITCH = (MODE == MODE_PW || MODE == MODE_PWR || MODE == MODE_N) ? 32 : (MODE == MODE_S2 ? 80 : (MODE == MODE_S1F ? 36 : (MODE == MODE_BRF ? 34 : (MODE == MODE_S1Q ? 40 : 48))));  // halo row pitch (pixels)
+    static constexpr int PITCH = (MODE == MODE_PW || MODE == MODE_N) ? 32 : (MODE == MODE_S2 ? 80 : (MODE == MODE_S1F ? 36 : (MODE == MODE_S1Q ? 40 : 48)));  // halo row pitch (pixels)
 };
 
 template <int TH, int BN, int WM, int WN>
@@ -296,24 +286,19 @@ __device__ __forceinline__ void wait_frags(frag_t (&w)[WN], frag_t (&p)[WM]) {
     else
         asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(w[0]), "+v"(p[0]) : "n"(N));
 }
-#ifdef CPN_EXP_NOVMWAIT  // tuning ablation (races by construction): the step boundary does not wait for the DMA
-#define CPN_WAIT_ALL_ASM "s_waitcnt lgkmcnt(0)"
-#else
-#define CPN_WAIT_ALL_ASM "s_waitcnt vmcnt(0) lgkmcnt(0)"
-#endif
 // step boundary: all my DMA landed + all my LDS reads returned (fragment set named "+v" as above)
 template <int WN, int WM>
 __device__ __forceinline__ void wait_all(frag_t (&w)[WN], frag_t (&p)[WM]) {
     if constexpr (WN == 2 && WM == 4)
-        asm volatile(CPN_WAIT_ALL_ASM : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]) :: "memory");
     else if constexpr (WN == 2 && WM == 2)
-        asm volatile(CPN_WAIT_ALL_ASM : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]), "+v"(p[1]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]), "+v"(p[1]) :: "memory");
     else if constexpr (WN == 2 && WM == 1)
-        asm volatile(CPN_WAIT_ALL_ASM : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(p[0]) :: "memory");
     else if constexpr (WN == 1 && WM == 2)
-        asm volatile(CPN_WAIT_ALL_ASM : "+v"(w[0]), "+v"(p[0]), "+v"(p[1]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0]), "+v"(p[0]), "+v"(p[1]) :: "memory");
     else
-        asm volatile(CPN_WAIT_ALL_ASM : "+v"(w[0]), "+v"(p[0]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(w[0]), "+v"(p[0]) :: "memory");
 }
 template <int WN, int WM, int FRAG_STRIDE>
 __device__ __forceinline__ void load_frags(frag_t (&w)[WN], frag_t (&p)[WM], unsigned paddr, unsigned waddr) {
@@ -327,25 +312,8 @@ __device__ __forceinline__ void load_frags(frag_t (&w)[WN], frag_t (&p)[WM], uns
     }
 }
 
-// pixel fragments only (MODE_S1R / MODE_PWR: the weight fragments come from global memory)
-template <int WM, int FRAG_STRIDE>
-__device__ __forceinline__ void load_pfrags(frag_t (&p)[WM], unsigned paddr) {
-    static_assert(WM == 4 || WM == 2, "register-weight loop: 128- or 64-pixel wave tile");
-    ds_read16<0>(p[0], paddr);
-    ds_read16<FRAG_STRIDE>(p[1], paddr);
-    if constexpr (WM > 2) {
-        ds_read16<2 * FRAG_STRIDE>(p[2], paddr);
-        ds_read16<3 * FRAG_STRIDE>(p[3], paddr);
-    }
-}
-template <int N, int WM>
-__device__ __forceinline__ void wait_pfrags(frag_t (&p)[WM]) {
-    if constexpr (WM == 4) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]) : "n"(N));
-    else asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(p[0]), "+v"(p[1]) : "n"(N));
-}
-
 // (FrameTiles / frame_tiles: cpn_kernels.h -- the executor's heuristic enumerates the same tiles)
-// wrap tiles apply to the stride-1 k x k modes (MODE_S1 / S1R / BL): the kernel and the launcher must agree
+// wrap tiles apply to the stride-1 k x k modes (MODE_S1 / BL): the kernel and the launcher must agree
 __host__ __device__ inline int frame_kw(const ConvArgs &a) { return (a.stride == 1 && !a.narrow && a.KW > 1) ? a.KW : 0; }
 
 struct ItemState {  // one K item = (32-channel chunk c, filter tap (ky, kx)); wave-uniform scalars
@@ -373,19 +341,18 @@ __device__ unsigned long long g_clock_probe[15];
 #endif
 
 template <int TH, int BN, int WM, int WN, int MODE>
-__global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE_S1F || MODE == MODE_BRF) ? 2 : 1)) void conv_igemm_kernel(const ConvArgs a) {
+__global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), (MODE == MODE_S1F ? 2 : 1)) void conv_igemm_kernel(const ConvArgs a) {
 #if defined(CPN_EXP_CLOCK) && CPN_EXP_CLOCK == 1
     const unsigned long long clk_entry = __builtin_readcyclecounter();
 #endif
     using C = Cfg<TH, BN, WM, WN>;
     constexpr int S = ModeCfg<MODE>::S;
     constexpr int PITCH = ModeCfg<MODE>::PITCH;
-    constexpr bool PW = MODE == MODE_PW || MODE == MODE_PWR;
+    constexpr bool PW = MODE == MODE_PW;
     constexpr bool BL = MODE == MODE_BL;
-    constexpr bool RW = MODE == MODE_S1R || MODE == MODE_PWR;  // weights: global -> registers (no weight tiles in LDS)
-    constexpr bool FL = MODE == MODE_S1F || MODE == MODE_BRF || MODE == MODE_S1Q;  // flat halo tile (pitch 36 | 34 | 40)
+    constexpr bool FL = MODE == MODE_S1F || MODE == MODE_S1Q;  // flat halo tile (pitch 36 | 40)
     constexpr int IPS = MODE == MODE_S1Q ? 4 : 2;  // K items per pipeline step
-    constexpr bool BR = MODE == MODE_BR || MODE == MODE_BRF;   // halo tiles computed in the kernel by the scattered phase conv in front (bridge fusion)
+    constexpr bool BR = MODE == MODE_BR;   // halo tiles computed in the kernel by the scattered phase conv in front (bridge fusion)
     constexpr bool NR = MODE == MODE_N;  // narrow output: fragment = 2 rows x 16 px; a.Hout / a.Wout are the virtual [H/2][32]
     constexpr int RPF = NR ? 2 : 1;      // output rows per pixel fragment
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -430,15 +397,9 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
             // (block id mod 8 = XCD): bid = (group of 8 tiles, cout block, tile within the group) -- they read the same halo
             // tiles through one L2 (ideally as the two residents of one CU) instead of a whole grid sweep apart
             const int nh = (a.cout_b + BN - 1) / BN;
-#ifdef CPN_EXP_S1F_MAP  // tuning ablation: 1 = cout blocks on ADJACENT block ids (different XCDs), 2 = cout-block-major (a grid sweep apart)
-            const int nt8 = ((tiles_x * tiles_y * a.N + 7) / 8) * 8;
-            if (CPN_EXP_S1F_MAP == 1) { yblk = bid % nh; bid = bid / nh; }
-            else { yblk = bid / nt8; bid = bid % nt8; }
-#else
             const int j = bid & 7, r = bid >> 3;
             yblk = r % nh;
             bid = (r / nh) * 8 + j;
-#endif
             if (bid >= tiles_x * tiles_y * a.N) return;  // (grid rounded up to whole groups of 8 tiles)
         }
         tx = bid % tiles_x;
@@ -480,9 +441,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     HaloGeo G;
     G.sub = PW ? a.stride : 1;
     G.n = n; G.iy0 = RPF * oy0 * (PW ? a.stride : S) - pad_y; G.ix0 = ox0 * (PW ? a.stride : S) - pad_x;
-#ifdef CPN_EXP_HALO_SAMETILE  // (tuning ablation, wrong results: every workgroup stages the input tile of workgroup 0 -> the halo DMA hits the L2)
-    G.n = 0; G.iy0 = -pad_y; G.ix0 = -pad_x;
-#endif
     G.Hin = a.Hin; G.Win = a.Win;
     G.up0 = a.up0; G.up1 = a.up1;
     G.Hs0 = a.Hs0; G.Ws0 = a.Ws0; G.Hs1 = a.Hs1; G.Ws1 = a.Ws1;
@@ -559,19 +517,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     }
 
 #define HALO_DMA(CHUNK) HALO_DMA_RANGE(CHUNK, 0, hinstr)
-    // cache policy of the activation / weight DMA (kernel A/B: -DCPN_HALO_AUX=2 = nt ...) and the traffic-free ablation of the halo DMA
-#ifndef CPN_HALO_AUX
-#define CPN_HALO_AUX 0
-#endif
-#ifndef CPN_W_AUX
-#define CPN_W_AUX 0
-#endif
-#ifndef CPN_EXP_HALO_OOB
-#define CPN_EXP_HALO_OOB 0
-#endif
-#ifndef CPN_EXP_HALO_NOISSUE  // (tuning ablation, wrong results: the halo path computes its addresses but issues no DMA instruction)
-#define CPN_EXP_HALO_NOISSUE 0
-#endif
 
     // instructions [Q0, Q1) of the halo tile of chunk CHUNK
 #define HALO_DMA_RANGE(CHUNK, Q0, Q1)                                                                          \
@@ -582,7 +527,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         unsigned char *dstb_ = smem + (c_ & nhb_mask) * halo_buf;                                              \
         _Pragma("unroll") for (int it_ = 0; it_ < FQ; ++it_) {                                                 \
             const int q_ = wave + it_ * C::NWAVES;                                                             \
-            if (q_ < hinstr) bdma16<CPN_HALO_AUX>(rs0, f_voff[it_], s_, dstb_ + (q_ << 10));                   \
+            if (q_ < hinstr) bdma16<0>(rs0, f_voff[it_], s_, dstb_ + (q_ << 10));                              \
         }                                                                                                      \
     } else HALO_DMA_RANGE_ROWS(CHUNK, Q0, Q1)
 
@@ -615,11 +560,10 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
                 const int ys_ = __builtin_amdgcn_readfirstlane(up_ ? nearest_src(iy_, sy_, Hs_) : iy_);        \
                 unsigned v_ = col_[0];                                                                         \
                 _Pragma("unroll") for (int j_ = 1; j_ < IPR; ++j_) v_ = seg_ == j_ ? col_[j_] : v_;           \
-                v_ = (ok_ && !CPN_EXP_HALO_OOB) ? v_ : OOB_LANE;  /* rows above / below the image: every lane reads zeros */ \
+                v_ = ok_ ? v_ : OOB_LANE;  /* rows above / below the image: every lane reads zeros */          \
                 const unsigned s_ = ok_ ? (unsigned) (img_ + ys_) * rowb_ + soff_ : 0u;                        \
-                if (CPN_EXP_HALO_NOISSUE) asm volatile("" :: "v"(v_), "s"(s_), "s"((unsigned) (size_t) (dstb_ + (q_ << 10)))); \
-                else if (from0_) bdma16<CPN_HALO_AUX>(rs0, v_, s_, dstb_ + (q_ << 10));                        \
-                else bdma16<CPN_HALO_AUX>(rs1, v_, s_, dstb_ + (q_ << 10));                                    \
+                if (from0_) bdma16<0>(rs0, v_, s_, dstb_ + (q_ << 10));                                        \
+                else bdma16<0>(rs1, v_, s_, dstb_ + (q_ << 10));                                               \
             }                                                                                                  \
         }                                                                                                      \
     }
@@ -630,14 +574,14 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         const unsigned soff_ = (unsigned) (cin0 + c_ * CH) * (unsigned) ES;                                    \
         unsigned char *dstb_ = smem + (c_ & nhb_mask) * halo_buf;                                              \
         _Pragma("unroll") for (int it = 0; it < A_INSTR_WAVE; ++it)                                            \
-            if (a_ok[it]) bdma16<CPN_HALO_AUX>(rs0, a_voff[it], soff_, dstb_ + ((wave + it * C::NWAVES) << 10)); \
+            if (a_ok[it]) bdma16<0>(rs0, a_voff[it], soff_, dstb_ + ((wave + it * C::NWAVES) << 10));          \
     }
 
     // stages the (two) weight slabs of the next step in order into weight buffer BUF
 #define W_DMA(BUF)                                                                                             \
-    if constexpr (!RW) {                                                                                       \
+    {                                                                                                          \
         _Pragma("unroll") for (int it = 0; it < W_IW; ++it)                                                    \
-            bdma16<CPN_W_AUX>(rsw, w_voff[it], wsoff + (unsigned) w_k[it] * item_bytes, smem + w_m0[it] + (BUF) * WBUF); \
+            bdma16<0>(rsw, w_voff[it], wsoff + (unsigned) w_k[it] * item_bytes, smem + w_m0[it] + (BUF) * WBUF); \
         wsoff += IPS * item_bytes;                                                                             \
     }
 
@@ -662,32 +606,12 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     const unsigned nr_lane = NR ? (unsigned) ((l31 >> 4) * S * PITCH * REC) : 0u;  // narrow: lanes 16..31 = the fragment's 2nd row
 
     // ---- software-pipelined main loop -------------------------------------------------------------------------
-#ifndef CPN_BACKEDGE_WAIT  // 1 (default): the bf16 loops close every iteration with lgkmcnt(0); 0: the first group's reads stay in flight
-#define CPN_BACKEDGE_WAIT 1  // across the back-edge; 2: the wait pinned behind the last MFMA group -- all three within +-1 % (r06 experiments #17)
-#endif
     // A step has up to four MFMA groups (item x k-half), each WN + WM fragments and WN*WM MFMAs.  Two fragment
     // register sets alternate (A: groups 0,2; B: groups 1,3): the ds_reads of group g+1 are issued BEFORE the MFMAs
     // of group g, so LDS latency hides behind the matrix pipe (ablation: the non-MFMA skeleton of the un-pipelined
     // loop cost 2.97 ms of the 5.33 ms of a 7x7 head conv and did not overlap with the MFMAs).  The step boundary
     // (vmcnt(0) + barrier + DMA issue for step s+2 + first fragment reads of step s+1) sits between the loads and
     // the MFMAs of the LAST group of step s, whose operands are already in registers.
-    // tuning experiments (profiles/): -DCPN_EXP_NOWDMA / -DCPN_EXP_NOHDMA skip the steady-state weight / halo DMA,
-    // -DCPN_EXP_NOMFMA keeps the fragment reads alive but issues no MFMA (results are wrong in all three)
-#ifdef CPN_EXP_NOWDMA
-#define CPN_EXP_W(x)
-#else
-#define CPN_EXP_W(x) x
-#endif
-#ifdef CPN_EXP_NOHDMA
-#define CPN_EXP_H(x)
-#else
-#define CPN_EXP_H(x) x
-#endif
-#ifdef CPN_EXP_NOMFMA
-#define CPN_EXP_MMA(ACC, A, B) asm volatile("" ::"v"(A), "v"(B))
-#else
-#define CPN_EXP_MMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, ACC, 0, 0, 0)
-#endif
 
     // byte address (within smem) of this lane's k-half-0 pixel / weight fragment of an item
 #define ITEM_PADDR(C_, KY_, KX_)                                                                               \
@@ -700,7 +624,8 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     {                                                                                                          \
         wait_frags<PENDING, WN, WM>(WF, PF);                                                                   \
         _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                         \
-            _Pragma("unroll") for (int f = 0; f < WM; ++f) CPN_EXP_MMA(acc[j][f], WF[j], PF[f]);               \
+            _Pragma("unroll") for (int f = 0; f < WM; ++f)                                                     \
+                acc[j][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(WF[j], PF[f], acc[j][f], 0, 0, 0);         \
     }
     // Branches of the step boundary that are taken once per chunk (or never: the 1x1 schedules of this instantiation): named unlikely,
     // hipcc places their blocks behind the loop and the common path falls through -- bf16 +0.5 ... +2.8 % (two taken long-distance
@@ -717,13 +642,13 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         const int idx2_ = IPS * (ST1) + IPS; /* first item of step ST1+1 */                                    \
         if (idx2_ < nitems) {                                                                                  \
             if (CPN_RARE(pw_fast)) {                                                                           \
-                if (idx2_ < nreal) { CPN_EXP_H(PW_HALO_DMA(idx2_)); }                                          \
-                if (idx2_ + 1 < nreal) { CPN_EXP_H(PW_HALO_DMA(idx2_ + 1)); }                                  \
+                if (idx2_ < nreal) { PW_HALO_DMA(idx2_); }                                                     \
+                if (idx2_ + 1 < nreal) { PW_HALO_DMA(idx2_ + 1); }                                             \
             } else if (CPN_RARE(pw)) {                                                                         \
-                if (idx2_ < nreal) { CPN_EXP_H(HALO_DMA(idx2_)); }                                             \
-                if (idx2_ + 1 < nreal) { CPN_EXP_H(HALO_DMA(idx2_ + 1)); }                                     \
+                if (idx2_ < nreal) { HALO_DMA(idx2_); }                                                        \
+                if (idx2_ + 1 < nreal) { HALO_DMA(idx2_ + 1); }                                                \
             }                                                                                                  \
-            CPN_EXP_W(W_DMA(((ST1) + 1) & 1));                                                                 \
+            W_DMA(((ST1) + 1) & 1);                                                                            \
         }                                                                                                      \
         /* KxK: every chunk before IA.c is completely consumed -> its ring buffer can take chunk IA.c+1 */     \
         CPN_HALO_AT_TRANSITION(IA, CHUNK_CHANGED)                                                              \
@@ -737,7 +662,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
 #define CPN_HALO_AT_TRANSITION(IA, CHUNK_CHANGED)                                                              \
     if (CPN_RARE(!pw && (CHUNK_CHANGED) && (IA).c + 1 < nchunks)) {                                            \
         if constexpr (BL) bl_pending = (IA).c + 1;                                                             \
-        else { CPN_EXP_H(HALO_DMA((IA).c + 1)); }                                                              \
+        else { HALO_DMA((IA).c + 1); }                                                                         \
     }
 #define CPN_BL_FLUSH()                                                                                         \
     if constexpr (BL) {                                                                                        \
@@ -780,14 +705,13 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     // low-resolution input tile staged by LDS-DMA.  Same K order (chunk-major, tap-minor, k-half-minor), bias, ReLU and bf16
     // rounding as the stand-alone op -> the main loop reads the bits the intermediate tensor would have held.
     if constexpr (BR) {
-        // TH = 16 (MODE_BR, 8 waves): 9 rows of every phase = 5 fragments, wave w = phase w >> 1 x channel block w & 1;
-        // TH = 8 (MODE_BRF, 4 waves, two workgroups per CU): 5 rows = 3 fragments, wave w = phase w x BOTH channel blocks
-        static_assert(BN == 64 && WM == 2 && WN == 2 && (TH == 16 || TH == 8), "bridge stage: the <16,64,2,2> / <8,64,2,2> tile");
+        // 8 waves: 9 rows of every phase = 5 fragments, wave w = phase w >> 1 x channel block w & 1
+        static_assert(TH == 16 && BN == 64 && WM == 2 && WN == 2, "bridge stage: the <16,64,2,2> tile");
         constexpr int NR1 = TH / 2 + 1, NPX1 = NR1 * 17, NF1 = (NPX1 + 31) / 32;   // rows, pixels, fragments of a phase
-        constexpr int NJ = TH == 16 ? 1 : 2;                                        // channel blocks per wave
+        static_assert(NF1 == 5, "the counted wait of the stage names five fragments");
         constexpr int PR = NR1 + 2, PC = 20, PREC = PR * PC, PINSTR = (PREC + 15) / 16;   // input tile (records of 64 B)
         constexpr int PBUF = PINSTR * 1024;
-        unsigned char *const pin = smem + ldsW_off + 2 * WBUF + (FL ? 0 : 2 * IPR * 256);
+        unsigned char *const pin = smem + ldsW_off + 2 * WBUF + 2 * IPR * 256;  // (behind the column table's place)
         const int pch = a.pre_cin >> 5;
         const int ly0 = (oy0 >> 1) - 2, lx0 = (ox0 >> 1) - 2;     // low-resolution pixel of input-tile record (0, 0)
         const rsrc_t rsp = make_rsrc(a.pre_src, (unsigned) ((size_t) a.N * a.pre_H * a.pre_W * a.pre_stride * ES));
@@ -802,22 +726,20 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
                 bdma16(rsp, vo, so, pin + c * PBUF + (q << 10));
             }
         }
-        // this wave's stage-1 weights: its phase, its channel block(s), per (chunk, tap) item two k-halves from L2 straight into
+        // this wave's stage-1 weights: its phase, its channel block, per (chunk, tap) item two k-halves from L2 straight into
         // registers (the packed slab rows ARE the A-fragment rows), requested step by step (all sixteen up front measured 3.5 %
         // slower: 214 instead of 171 registers and one L2 burst per tile); the first weight slabs of the MAIN loop are requested
         // here, in front of the stage, instead of behind it
-        const int ph = TH == 16 ? wave >> 1 : wave, jb0 = TH == 16 ? (wave & 1) : 0, py = ph >> 1, px = ph & 1;
+        const int ph = wave >> 1, jb = wave & 1, py = ph >> 1, px = ph & 1;
         const int l31b = lane & 31, lhib = lane >> 5;
         W_DMA(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        f32x16 acc1[NJ][NF1];
+        f32x16 acc1[NF1];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
+        for (int f = 0; f < NF1; ++f)
 #pragma unroll
-            for (int f = 0; f < NF1; ++f)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc1[j][f][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc1[f][r] = 0.f;
         // output pixel o = 32 f + lane of this phase = (ri, rj) of its NR1 x 17 grid = low-resolution pixel ((oy0 >> 1) - py + ri,
         // (ox0 >> 1) - px + rj); its tap (ty, tx) reads input row i - 1 + py + ty = input-tile row ri + 1 + ty (likewise the columns)
         int ri[NF1], rj[NF1];
@@ -831,20 +753,14 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         }
         const int nit1 = 4 * pch;  // items of a phase bundle (even)
         const unsigned lds_pin = (unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) pin;
-        const unsigned char *const w1 = (const unsigned char *) a.pre_w + ((size_t) ph * nit1 * 64 + jb0 * 32 + l31b) * REC + (lhib << 4);
+        const unsigned char *const w1 = (const unsigned char *) a.pre_w + ((size_t) ph * nit1 * 64 + jb * 32 + l31b) * REC + (lhib << 4);
         // (one fragment set: the two waves of a SIMD belong to different phases / workgroups and cover each other's read latency)
         frag_t pa0[NF1], pa1[NF1];
 #pragma unroll
         for (int s1 = 0; s1 < 8; ++s1) {   // K step s1 = (chunk s1 >> 2, tap s1 & 3): k-half 0 and 1
             if (s1 < nit1) {
-                frag_t wA[NJ][2];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const unsigned char *wp = w1 + ((size_t) s1 * 64 + j * 32) * REC;
-                    wA[j][0] = *(const frag_t *) wp;
-                    wA[j][1] = *(const frag_t *) (wp + 32);
-                }
-#ifndef CPN_BR_NOSTAGE1  // (ablation: no stage-1 reads / MFMAs -- wrong results by construction)
+                const unsigned char *wp = w1 + (size_t) s1 * 64 * REC;
+                const frag_t wA0 = *(const frag_t *) wp, wA1 = *(const frag_t *) (wp + 32);
                 const int toff = ((s1 >> 1) & 1) * PC + (s1 & 1);
 #pragma unroll
                 for (int f = 0; f < NF1; ++f) {
@@ -853,27 +769,21 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
                     ds_read16<0>(pa0[f], ad);
                     ds_read16<0>(pa1[f], ad ^ 32u);
                 }
-                if constexpr (NF1 == 5)
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pa0[0]), "+v"(pa0[1]), "+v"(pa0[2]), "+v"(pa0[3]), "+v"(pa0[4]),
-                                 "+v"(pa1[0]), "+v"(pa1[1]), "+v"(pa1[2]), "+v"(pa1[3]), "+v"(pa1[4]));
-                else
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pa0[0]), "+v"(pa0[1]), "+v"(pa0[2]), "+v"(pa1[0]), "+v"(pa1[1]), "+v"(pa1[2]));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pa0[0]), "+v"(pa0[1]), "+v"(pa0[2]), "+v"(pa0[3]), "+v"(pa0[4]),
+                             "+v"(pa1[0]), "+v"(pa1[1]), "+v"(pa1[2]), "+v"(pa1[3]), "+v"(pa1[4]));
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
+                for (int f = 0; f < NF1; ++f) acc1[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA0, pa0[f], acc1[f], 0, 0, 0);
 #pragma unroll
-                    for (int f = 0; f < NF1; ++f) acc1[j][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA[j][0], pa0[f], acc1[j][f], 0, 0, 0);
-#pragma unroll
-                    for (int f = 0; f < NF1; ++f) acc1[j][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA[j][1], pa1[f], acc1[j][f], 0, 0, 0);
-                }
-#endif
+                for (int f = 0; f < NF1; ++f) acc1[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wA1, pa1[f], acc1[f], 0, 0, 0);
             }
         }
         // bias + ReLU -> bf16 -> the main loop's halo record of (row 1 - py + 2 ri, column 1 - px + 2 rj), chunk = channel block;
         // pixels outside the image are the 3x3 conv's zero padding
         typedef __attribute__((address_space(3))) u32x2 lds_u32x2_t;
+        // (a one-trip loop, left from the variant whose waves owned both channel blocks: without it hipcc schedules the bias loads
+        // differently, and this kernel's code is to stay what profiles/ measured)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int jb = jb0 + j;
+        for (int once = 0; once < 1; ++once) {
             float b1[4][4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -892,7 +802,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        v[e] = acc1[j][f][q * 4 + e] + b1[q][e];
+                        v[e] = acc1[f][q * 4 + e] + b1[q][e];
                         v[e] = in_img ? __int_as_float(max(__float_as_int(v[e]), 0)) : 0.f;   // (the stand-alone epilogue's ReLU)
                     }
                     u32x2 w2;
@@ -934,7 +844,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     }
     unsigned pa = ITEM_PADDR(i0.c, i0.ky, i0.kx);
     unsigned wa = (unsigned) ldsW_off + w_lane;
-#ifndef CPN_FP8_HALFSETS
     // Round 6: WHOLE operand sets alternate (set 0 = X|Y of a step's first item, set 1 = of its second): the twelve reads of the
     // next item are issued in front of the eight MFMAs of the current one, so no MFMA group waits for a read that was issued right
     // in front of it.  (Rounds 3-5 alternated half sets -- Y of item i and X of item i+1 in flight per group: the MFMAs of item 0
@@ -952,14 +861,12 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     LOAD_GROUP(wX0, pX0, pa, wa);
     LOAD_GROUP(wY0, pY0, pa ^ 16u, wa ^ 16u);
     for (int st = 0; st + 1 < nsteps; ++st) {
-#if CPN_WAVE_PRIO
         // Alternating wave priority (round 6): the two waves of a SIMD (w and w + NWAVES / 2) share its matrix pipe, arbitrated by
         // priority, then AGE -- at equal priority the older wave's MFMAs always go first, it reaches the barrier ~900 cycles before
         // its partner (s_memtime stamps, profiles/r06_kernel_experiments.txt) and idles there while the partner runs its remaining
         // MFMA groups and gaps alone.  From the barrier to the middle of a step the younger half has priority, from there to the
         // barrier the older half: each wave gets its MFMA groups through while the other is in its DMA-issue / fragment-read gaps.
         if (prio_wave) { if (wave >= C::NWAVES / 2) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
-#endif
         const unsigned pa1 = ITEM_PADDR(i1.c, i1.ky, i1.kx), wa1 = wa + WITEM;
         LOAD_GROUP(wX1, pX1, pa1, wa1);               // item 1 (both parts) in flight behind ...
         LOAD_GROUP(wY1, pY1, pa1 ^ 16u, wa1 ^ 16u);
@@ -972,12 +879,8 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         const ItemState n0i = next_item(i1, KH, KW);  // first item of step st+1
         wait_all<WN, WM>(wY1, pY1);                   // my DMA for step st+1 landed, all my LDS reads returned
         wait_frags<0, WN, WM>(wX1, pX1);              // (names the X set of item 1 as complete, too)
-#ifndef CPN_EXP_NOBAR  // (tuning ablation: wrong results)
         __builtin_amdgcn_s_barrier();
-#endif
-#if CPN_WAVE_PRIO
         if (prio_wave) { if (wave >= C::NWAVES / 2) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-#endif
         if constexpr (WM == 4 && WN == 2) {
             MMA4(wX1, wY1, pX1, pY1, 0);              // item 1, first weight fragment (operands in registers)
             PIN_ACC(0);
@@ -1008,125 +911,9 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     }
 #undef MMA4
 #undef PIN_ACC
-#else
-    LOAD_GROUP(wX0, pX0, pa, wa);
-    wait_frags<0, WN, WM>(wX0, pX0);
-    for (int st = 0; st + 1 < nsteps; ++st) {
-        LOAD_GROUP(wY0, pY0, pa ^ 16u, wa ^ 16u);     // item 0, second part
-        const unsigned pa1 = ITEM_PADDR(i1.c, i1.ky, i1.kx), wa1 = wa + WITEM;
-        LOAD_GROUP(wX1, pX1, pa1, wa1);               // item 1, first part
-        MMA8(wX0, wY0, pX0, pY0, NF);                 // item 0
-        LOAD_GROUP(wY1, pY1, pa1 ^ 16u, wa1 ^ 16u);   // item 1, second part
-        const ItemState n0i = next_item(i1, KH, KW);  // first item of step st+1
-        wait_all<WN, WM>(wY1, pY1);                   // my DMA for step st+1 landed, all my LDS reads returned
-        wait_frags<0, WN, WM>(wX1, pX1);              // (names the X set of item 1 as complete, too)
-        __builtin_amdgcn_s_barrier();
-        ISSUE_AT_TRANSITION(n0i, st + 1, n0i.c != i0.c);
-        pa = ITEM_PADDR(n0i.c, n0i.ky, n0i.kx);
-        wa = (unsigned) (ldsW_off + ((st + 1) & 1) * WBUF) + w_lane;
-        LOAD_GROUP(wX0, pX0, pa, wa);                 // first part of step st+1
-        MMA8(wX1, wY1, pX1, pY1, NF);                 // item 1 (operands already in registers)
-        wait_frags<0, WN, WM>(wX0, pX0);
-        CPN_BL_FLUSH();
-        i0 = n0i;
-        i1 = next_item(n0i, KH, KW);
-    }
-    {   // last step (two items: an odd item count was padded with a zero slab)
-        LOAD_GROUP(wY0, pY0, pa ^ 16u, wa ^ 16u);
-        const unsigned pa1 = ITEM_PADDR(i1.c, i1.ky, i1.kx), wa1 = wa + WITEM;
-        LOAD_GROUP(wX1, pX1, pa1, wa1);
-        MMA8(wX0, wY0, pX0, pY0, NF);
-        LOAD_GROUP(wY1, pY1, pa1 ^ 16u, wa1 ^ 16u);
-        wait_frags<NF, WN, WM>(wX1, pX1);
-        MMA8(wX1, wY1, pX1, pY1, 0);
-    }
-#endif
 #undef MMA8
 #undef CAT8
 #else
-    if constexpr (RW) {
-        // ---- MODE_S1R: weight fragments straight from L2 into registers in MFMA layout (the packed slab rows are the
-        // fragment rows; lane -> row l31 of the 32-row fragment, 16-byte part 2*khalf + lhi, same swizzle as the LDS
-        // tiles).  Four register sets (item 0/1 x k-half 0/1) are refilled for the step after next as soon as their
-        // MFMAs have issued: ~1.75 items of prefetch distance, vmcnt tracked by the compiler.  The LDS holds only
-        // the halo tiles: one third fewer LDS reads, no weight DMA, and the workgroup barrier is needed only twice
-        // per 32-channel chunk (buffer hand-over + tile landed) instead of once per step.
-        frag_t W0a[WN], W0b[WN], W1a[WN], W1b[WN], pA[WM], pB[WM];
-        // (the packed slabs are not swizzled: part p of a row lives at byte 16 p; the XOR swizzle is applied by the DMA path only)
-        const unsigned wl0 = (unsigned) ((wave_n * WN * 32 + l31) * REC + (lhi << 4)), wl1 = wl0 + 32u;
-#define VLOADW(DST, WL, SOFF)                                                                                  \
-    _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                             \
-        DST[j] = __builtin_bit_cast(frag_t, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int) ((WL) + j * 32 * REC), (int) (SOFF), 0))
-#define LOADP(PF, PADDR) load_pfrags<WM, FRAG_STRIDE>(PF, lds0 + (PADDR))
-#define MMAP(WF, PF, PENDING)                                                                                  \
-    {                                                                                                          \
-        wait_pfrags<PENDING, WM>(PF);                                                                          \
-        _Pragma("unroll") for (int j = 0; j < WN; ++j)                                                         \
-            _Pragma("unroll") for (int f = 0; f < WM; ++f) CPN_EXP_MMA(acc[j][f], WF[j], PF[f]);               \
-    }
-        unsigned so = wsoff;  // slab of the first item of the current step
-        VLOADW(W0a, wl0, so); VLOADW(W0b, wl1, so);
-        VLOADW(W1a, wl0, so + item_bytes); VLOADW(W1b, wl1, so + item_bytes);
-        unsigned pa = ITEM_PADDR(i0.c, i0.ky, i0.kx);
-        LOADP(pA, pa);
-        bool land_due = nchunks > 1;  // chunk 1's tile was issued in the prologue
-        for (int st = 0; st + 1 < nsteps; ++st) {
-            so += 2 * item_bytes;
-            LOADP(pB, pa ^ 32u);
-            MMAP(W0a, pA, WM);
-            VLOADW(W0a, wl0, so);
-            pa = ITEM_PADDR(i1.c, i1.ky, i1.kx);
-            LOADP(pA, pa);
-            MMAP(W0b, pB, WM);
-            VLOADW(W0b, wl1, so);
-            LOADP(pB, pa ^ 32u);
-            MMAP(W1a, pA, WM);
-            VLOADW(W1a, wl0, so + item_bytes);
-            const ItemState n0i = next_item(i1, KH, KW);
-            const bool changed = n0i.c != i0.c;
-            if (changed || land_due) {
-                // all my reads of the finished chunk returned; my halo DMA of the previous hand-over (>= 8 weight loads
-                // older than now: VMEM returns in order) landed; after the barrier that holds for every wave
-                wait_pfrags<0, WM>(pB);
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                land_due = false;
-                if constexpr (PW) {
-                    // pointwise: every item is a chunk of its own -- stage the two chunks of step st + 2 into the ring
-                    // slots step st occupied (everybody's reads of step st returned: barrier above)
-                    const int idx2_ = 2 * (st + 1) + 2;
-                    if (idx2_ < nreal) {
-                        if (pw_fast) { PW_HALO_DMA(idx2_); } else { HALO_DMA(idx2_); }
-                        land_due = true;
-                    }
-                    if (idx2_ + 1 < nreal) {
-                        if (pw_fast) { PW_HALO_DMA(idx2_ + 1); } else { HALO_DMA(idx2_ + 1); }
-                    }
-                } else if (changed && n0i.c + 1 < nchunks) {
-                    HALO_DMA(n0i.c + 1);
-                    land_due = true;
-                }
-            }
-            pa = ITEM_PADDR(n0i.c, n0i.ky, n0i.kx);
-            LOADP(pA, pa);
-            MMAP(W1b, pB, WM);
-            VLOADW(W1b, wl1, so + item_bytes);
-            wait_pfrags<0, WM>(pA);
-            i0 = n0i;
-            i1 = next_item(n0i, KH, KW);
-        }
-        LOADP(pB, pa ^ 32u);
-        MMAP(W0a, pA, WM);
-        pa = ITEM_PADDR(i1.c, i1.ky, i1.kx);
-        LOADP(pA, pa);
-        MMAP(W0b, pB, WM);
-        LOADP(pB, pa ^ 32u);
-        MMAP(W1a, pA, WM);
-        MMAP(W1b, pB, 0);
-#undef VLOADW
-#undef LOADP
-#undef MMAP
-    } else {
     frag_t wA[WN], pA[WM], wB[WN], pB[WM];
     constexpr int NF = WN + WM;  // ds_reads per group
     unsigned pa = ITEM_PADDR(i0.c, i0.ky, i0.kx);
@@ -1169,9 +956,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         wa = (unsigned) (ldsW_off + ((st + 1) & 1) * WBUF) + w_lane;
         LOAD_GROUP(wA, pA, pa, wa);                   // first group of step st+1
         MMA_GROUP(wB, pB, NF);                        // item 3, k-half 1 (operands already in registers)
-#if CPN_BACKEDGE_WAIT == 1                            // (see the two-item loop below)
-        wait_frags<0, WN, WM>(wA, pA);
-#endif
+        wait_frags<0, WN, WM>(wA, pA);                // (see the two-item loop below)
     }
     QSTEP_HEAD();                                     // last step
     MMA_GROUP(wB, pB, 0);
@@ -1180,9 +965,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     } else {
     // every step that is followed by another step holds two items: the loop body is branch-free with respect to
     // the accumulators and fragment sets (conditional MFMA groups made hipcc rename/spill accumulators)
-#define PIN_ACC_ALL()                                                                                          \
-    _Pragma("unroll") for (int j_ = 0; j_ < WN; ++j_)                                                          \
-        _Pragma("unroll") for (int f_ = 0; f_ < WM; ++f_) asm volatile("" : "+v"(acc[j_][f_]))
     for (int st = 0; st + 1 < nsteps; ++st) {
         LOAD_GROUP(wB, pB, pa ^ 32u, wa ^ 32u);      // item 0, k-half 1
         MMA_GROUP(wA, pA, NF);                        // item 0, k-half 0
@@ -1201,12 +983,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         wa = (unsigned) (ldsW_off + ((st + 1) & 1) * WBUF) + w_lane;
         LOAD_GROUP(wA, pA, pa, wa);                   // first group of step st+1
         MMA_GROUP(wB, pB, NF);                        // last group of step st (operands already in registers)
-#if CPN_BACKEDGE_WAIT == 1
         wait_frags<0, WN, WM>(wA, pA);                // nothing is in flight across the loop back-edge
-#elif CPN_BACKEDGE_WAIT == 2
-        PIN_ACC_ALL();                                // the same wait, held behind the eight MFMAs of the group
-        wait_frags<0, WN, WM>(wA, pA);
-#endif
         CPN_BL_FLUSH();
         i0 = n0i;
         i1 = next_item(n0i, KH, KW);
@@ -1221,7 +998,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     LOAD_GROUP(wB, pB, pa ^ 32u, wa ^ 32u);
     MMA_GROUP(wA, pA, NF);
     MMA_GROUP(wB, pB, 0);
-    }
     }
 #endif
 #undef HALO_DMA
@@ -1252,7 +1028,7 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
         // matrix-pipe cycles the loop's MFMAs occupy on one SIMD x 4: a 32x32x16 bf16 MFMA = 32 cycles, 2 k-halves x WN x WM per item
         // and wave, NWAVES / 4 waves per SIMD, two co-resident workgroups in the flat modes
         const unsigned long long pipe4 = (unsigned long long) nsteps * IPS * (2 * WN * WM * 32) * C::NWAVES *
-                                         ((MODE == MODE_S1F || MODE == MODE_BRF) ? 2 : 1);
+                                         (MODE == MODE_S1F ? 2 : 1);
         atomicAdd(g, dc); atomicAdd(g + 1, dr); atomicAdd(g + 2, (unsigned long long) nsteps); atomicAdd(g + 3, 1ull);
         atomicAdd(g + 4, pipe4);
 #else
@@ -1262,9 +1038,6 @@ __global__ __launch_bounds__((64 * (TH / WM) * (BN / (32 * WN))), ((MODE == MODE
     }
 #endif
     // ---- epilogue
-#ifdef CPN_EXP_NOEPI
-    if (a.N < 0)
-#endif
     if (a.out_mode == OUT_BF16_NHWC) {
         // NHWC bf16 output through a per-wave fp32 LDS staging tile: the MFMA D layout gives every lane 4 channels of
         // 16 different pixels (8-byte pieces of sixteen 128-B lines: measured 20-70 % of the run time of the 1x1 /
@@ -1643,7 +1416,7 @@ namespace CPN_NS {
 static bool flat_ok(const ConvArgs &a) {
     if (CPN_FP8) return false;
     const char *e = getenv("CPN_S1F");
-    const int mode = e ? atoi(e) : CPN_S1F_DEFAULT;
+    const int mode = e ? atoi(e) : 1;
     if (mode == 0) return false;
     const bool shape = a.stride == 1 && a.KH >= 2 && a.KH <= 5 && a.KW >= 2 && a.KW <= 5 && !a.src1 && !a.up0 && !a.up1 &&
                        a.region == 0 && !a.narrow && a.out_mode == OUT_BF16_NHWC && a.cout_b % 128 == 0 && a.Hout >= 8;
@@ -1667,35 +1440,23 @@ static bool quad_ok(const ConvArgs &a) {
            (long) ((a.Wout + TW - 1) / TW) * ((a.Hout + 15) / 16) * a.N >= 448;
 }
 
-static int conv_mode(const ConvArgs &a) {
+// the kernel variant of a conv: decided ONCE per launch (the two checks above read their switches) and handed to
+// lds_bytes / choose_tile / launch_cfg
+static Mode conv_mode(const ConvArgs &a) {
     if (a.pre_src) return MODE_BR;
     if (quad_ok(a)) return MODE_S1Q;
     if (a.narrow) return MODE_N;
     if (flat_ok(a)) return MODE_S1F;
-    if (a.KH == 1 && a.KW == 1 && a.pad == 0) {  // incl. strided 1x1: the tile gathers only its outputs
-        const char *e = getenv("CPN_PWR");  // opt-in experiment (read per call): register-weight loop, 8x256 tile only
-        return (!CPN_FP8 && e && atoi(e) != 0) ? MODE_PWR : MODE_PW;
-    }
+    if (a.KH == 1 && a.KW == 1 && a.pad == 0) return MODE_PW;  // incl. strided 1x1: the tile gathers only its outputs
     if (a.up0 == 2) return MODE_BL;
     if (a.stride == 2) return MODE_S2;
-    // MODE_S1R (register-weight loop; CPN_RW read per call so that tests can toggle it), bit 0: the 8x256 tile -- opt-in: on
-    // random operands it runs within 1 % of the LDS-weight loop (both sit on the same power wall), on all-zero operands 7x7
-    // +8 % / 3x3 -4 %; bit 1: the 64-channel tiles (2 weight + 2 pixel fragment reads per 4 MFMAs in the LDS-weight
-    // loop -> 2 pixel reads; every wave streams the 8 KiB of a 64 -> 64 tap from L2 itself)
-    const char *e = getenv("CPN_RW");
-    const int rw = e ? atoi(e) : CPN_RW_DEFAULT;
-    if (CPN_FP8 || a.KH * a.KW < 9) return MODE_S1;
-    if (a.cout_b == 64 && a.bundles == 1) return (rw & 2) ? MODE_S1R : MODE_S1;
-    return (rw & 1) ? MODE_S1R : MODE_S1;  // (taken by the 8x256 tile only)
+    return MODE_S1;
 }
 
-static size_t lds_bytes(const ConvArgs &a, int TH, int BN) {
-    const int mode = conv_mode(a);
+static size_t lds_bytes(const ConvArgs &a, Mode mode, int TH, int BN) {
     const int S = mode == MODE_S2 ? 2 : 1;
     if (mode == MODE_BR) {  // two halo tiles of a 3x3 conv + slabs + the low-resolution input tile of the bridge stage (two chunks)
         const size_t pin = 2 * (size_t) (((TH / 2 + 3) * 20 + 15) / 16) * 1024;
-        if (TH == 8)  // MODE_BRF: flat pitch-34 halo tiles, no column table: 22 + 22 + 16 + 18 = 78 KiB -> two workgroups per CU
-            return 2 * (size_t) (((TH - 1 + 3) * 34 * 4 + 63) / 64) * 1024 + 2 * 2 * (size_t) BN * REC + pin;
         return 2 * (size_t) (((TH - 1 + 3) * 48 * 4 + 63) / 64) * 1024 + 2 * 2 * (size_t) BN * REC + 2 * 3 * 256 + pin;
     }
     if (mode == MODE_S1Q)  // flat pitch-40 halo tiles (two chunks in flight), four items x two buffers of slabs, no column table
@@ -1704,7 +1465,7 @@ static size_t lds_bytes(const ConvArgs &a, int TH, int BN) {
         const size_t halo_buf = (size_t) (((TH - 1 + a.KH) * 36 * 4 + 63) / 64) * 1024;
         return (a.cin_b / 32 > 1 ? 2 : 1) * halo_buf + 2 * 2 * (size_t) BN * REC;
     }
-    const int pitch = (mode == MODE_PW || mode == MODE_PWR || mode == MODE_N) ? 32 : (mode == MODE_S2 ? 80 : 48);
+    const int pitch = (mode == MODE_PW || mode == MODE_N) ? 32 : (mode == MODE_S2 ? 80 : 48);
     const int HH = ((mode == MODE_N ? 2 : 1) * TH - 1) * S + a.KH;
     const int nchunks = a.cin_b / 32;
     const size_t halo_buf = (size_t) ((HH * pitch * 4 + 63) / 64) * 1024;
@@ -1718,10 +1479,10 @@ static size_t staging_bytes(int nwaves, int WN) { return (size_t) nwaves * 32 * 
 constexpr size_t LDS_MAX = 160 * 1024;
 constexpr int MAX_DEVICES = 64;
 
-template <int TH, int BN, int WM, int WN, int MODE>
+template <int TH, int BN, int WM, int WN, Mode MODE>
 static int launch_mode(const ConvArgs &a, hipStream_t stream) {
     using C = Cfg<TH, BN, WM, WN>;
-    size_t lds = std::max(lds_bytes(a, TH, BN), staging_bytes(C::NWAVES, WN));
+    size_t lds = std::max(lds_bytes(a, MODE, TH, BN), staging_bytes(C::NWAVES, WN));
     if (a.out_mode == OUT_FUSED_HEAD) lds = std::max(lds, (size_t) TH * 32 * BN * 2 + 2 * (size_t) BN * 4 + (size_t) 32 * BN * 2);  // staging + bias / multiplier table + W2
     // the dynamic-LDS limit is a per-device function attribute: remember it per device ordinal (atomic flags: plans of
     // different devices / host threads may launch the same instantiation concurrently)
@@ -1737,8 +1498,8 @@ static int launch_mode(const ConvArgs &a, hipStream_t stream) {
     const int tiles_x = (a.Wout + TW - 1) / TW, tiles_y = (a.Hout + TH - 1) / TH;
     const int ntiles = a.region == 2 ? frame_tiles(a.Hout, a.Wout, a.region_margin, TH, TW, frame_kw(a)).total : tiles_x * tiles_y;
     dim3 grid((unsigned) (ntiles * a.N), (unsigned) ((a.cout_b + BN - 1) / BN), (unsigned) a.bundles);
-    if constexpr (MODE == MODE_S1F || MODE == MODE_BRF || MODE == MODE_S1Q) {  // cout blocks folded into x (see the kernel's block coordinates)
-        if (MODE != MODE_S1Q && lds > LDS_MAX / 2) return (int) hipErrorInvalidValue;  // (two workgroups per CU is the point of those modes)
+    if constexpr (MODE == MODE_S1F || MODE == MODE_S1Q) {  // cout blocks folded into x (see the kernel's block coordinates)
+        if (MODE == MODE_S1F && lds > LDS_MAX / 2) return (int) hipErrorInvalidValue;  // (two workgroups per CU is the point of that mode)
         grid = dim3((unsigned) (((ntiles * a.N + 7) / 8) * 8 * ((a.cout_b + BN - 1) / BN)), 1u, (unsigned) a.bundles);
     }
     hipLaunchKernelGGL(kern, grid, dim3(C::THREADS), lds, stream, a);
@@ -1746,58 +1507,37 @@ static int launch_mode(const ConvArgs &a, hipStream_t stream) {
 }
 
 template <int TH, int BN, int WM, int WN>
-static int launch_cfg(const ConvArgs &a, hipStream_t stream) {
-    switch (conv_mode(a)) {
-        case MODE_PWR:
-#if !CPN_FP8
-            if constexpr (TH == 8 && BN == 256 && WM == 4 && WN == 2) return launch_mode<TH, BN, WM, WN, MODE_PWR>(a, stream);
-#endif
-            return launch_mode<TH, BN, WM, WN, MODE_PW>(a, stream);
+static int launch_cfg(const ConvArgs &a, Mode mode, hipStream_t stream) {
+    switch (mode) {
         case MODE_PW: return launch_mode<TH, BN, WM, WN, MODE_PW>(a, stream);
 #if !CPN_FP8
         case MODE_N: return launch_mode<TH, BN, WM, WN, MODE_N>(a, stream);
 #endif
         case MODE_S1: return launch_mode<TH, BN, WM, WN, MODE_S1>(a, stream);
-        case MODE_S1R:
-#if !CPN_FP8
-            if constexpr ((TH == 8 && BN == 256 && WM == 4 && WN == 2) || (BN == 64 && WM == 2 && WN == 2))
-                return launch_mode<TH, BN, WM, WN, MODE_S1R>(a, stream);
-#endif
-            return launch_mode<TH, BN, WM, WN, MODE_S1>(a, stream);
+        case MODE_S2: return launch_mode<TH, BN, WM, WN, MODE_S2>(a, stream);
 #if !CPN_FP8  // bf16 only: the e4m3 kernel has no registers to spare for the in-register blend (it spilled, and ran at
               // 0.16 of its plain rate); fp8 plans keep the separate resize op, which moves half the bytes of a bf16 one
         case MODE_BL: return launch_mode<TH, BN, WM, WN, MODE_BL>(a, stream);
 #endif
-        default: return launch_mode<TH, BN, WM, WN, MODE_S2>(a, stream);
+        default: return (int) hipErrorInvalidValue;  // (MODE_S1F / S1Q / BR have one tile each: launch_conv; MODE_N / BL: bf16 only)
     }
 }
 
-static TileChoice choose_tile(const ConvArgs &a) {
+static TileChoice choose_tile(const ConvArgs &a, Mode mode) {
     int BN = a.cout_b >= 256 ? 256 : a.cout_b >= 128 ? 128 : a.cout_b >= 64 ? 64 : 32;
     int TH = 8;
     auto blocks = [&](int th, int bn) {
         return (long) ((a.Wout + TW - 1) / TW) * ((a.Hout + th - 1) / th) * a.N * ((a.cout_b + bn - 1) / bn) * a.bundles;
     };
-    if (lds_bytes(a, 8, BN) > LDS_MAX || a.Hout < 8) TH = 4;
+    if (lds_bytes(a, mode, 8, BN) > LDS_MAX || a.Hout < 8) TH = 4;
     // the big tiles have the best FLOP per L2 byte; shrink only while the grid cannot fill the 256 CUs once
     constexpr long MIN_BLOCKS = 224;
     if (TH == 8 && blocks(8, BN) < MIN_BLOCKS) TH = 4;
     if (blocks(TH, BN) < MIN_BLOCKS && BN > 128) BN = 128;
     if (blocks(TH, BN) < MIN_BLOCKS && BN > 64) BN = 64;
-    while (lds_bytes(a, TH, BN) > LDS_MAX && BN > 32) BN >>= 1;
+    while (lds_bytes(a, mode, TH, BN) > LDS_MAX && BN > 32) BN >>= 1;
     // narrow-channel layers at high resolution (64 -> 64 @ 512^2): 16-row tiles keep 8 waves per CU busy
-    // (CPN_TH64=8: kernel A/B switch, read per call -- 8-row tiles, two workgroups per CU where their LDS fits twice)
-    const char *e64 = getenv("CPN_TH64");
-    if (BN == 64 && TH == 8 && a.Hout >= 16 && lds_bytes(a, 16, 64) <= LDS_MAX && blocks(16, 64) >= 2 * MIN_BLOCKS &&
-        !(e64 && atoi(e64) == 8))
-        TH = 16;
-    // CPN_PW_TILE="TH,BN" (read per call): tile of the 1x1 convs -- kernel A/B (r06 experiments #20)
-    if (const char *ep = getenv("CPN_PW_TILE"); ep && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.out_mode == OUT_BF16_NHWC) {
-        int th = 0, bn = 0;
-        if (sscanf(ep, "%d,%d", &th, &bn) == 2 && (th == 4 || th == 8) && (bn == 64 || bn == 128 || bn == 256) && bn <= a.cout_b &&
-            a.Hout >= th && lds_bytes(a, th, bn) <= LDS_MAX)
-            return TileChoice{th, bn};
-    }
+    if (BN == 64 && TH == 8 && a.Hout >= 16 && lds_bytes(a, mode, 16, 64) <= LDS_MAX && blocks(16, 64) >= 2 * MIN_BLOCKS) TH = 16;
     return TileChoice{TH, BN};
 }
 
@@ -1823,44 +1563,41 @@ int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
 #if !CPN_FP8
     if (a.pre_src) {  // bridge fusion (see ConvArgs.pre_*): checked by conv_bridge_supported
         if (!conv_bridge_supported(a)) return (int) hipErrorInvalidValue;
-        // MODE_BRF (opt-in: CPN_BRF=1, read per call -- kernel A/B and tests): 8-row tiles on 4 waves, flat pitch-34 halo tiles,
-        // 78 KiB = two co-resident workgroups per CU.  Bit-identical, measured NEUTRAL against the <16,64,2,2> tile (580 vs 575 us,
-        // profiles/r05_kernel_experiments.txt #6): unlike the 256-channel decoder convs this kernel is not waiting on a tile's head
-        // and tail -- the default stays the one-workgroup tile
-        const char *e = getenv("CPN_BRF");
-        if (e && atoi(e) == 1) return launch_mode<8, 64, 2, 2, MODE_BRF>(a, stream);
         return launch_mode<16, 64, 2, 2, MODE_BR>(a, stream);
-    }
-    if (conv_mode(a) == MODE_S1F) return launch_mode<8, 128, 4, 2, MODE_S1F>(a, stream);
-    if (conv_mode(a) == MODE_S1Q) {
-        if (lds_bytes(a, 16, 64) > LDS_MAX) return (int) hipErrorInvalidValue;
-        return launch_mode<16, 64, 2, 2, MODE_S1Q>(a, stream);
     }
 #else
     if (a.pre_src) return (int) hipErrorInvalidValue;
 #endif
-    TileChoice c = choose_tile(a);
+    const Mode mode = conv_mode(a);
+#if !CPN_FP8
+    if (mode == MODE_S1F) return launch_mode<8, 128, 4, 2, MODE_S1F>(a, stream);
+    if (mode == MODE_S1Q) {
+        if (lds_bytes(a, mode, 16, 64) > LDS_MAX) return (int) hipErrorInvalidValue;
+        return launch_mode<16, 64, 2, 2, MODE_S1Q>(a, stream);
+    }
+#endif
+    TileChoice c = choose_tile(a, mode);
     if (a.out_mode == OUT_FUSED_HEAD) {  // the block must own all output channels; TH multiple of the wave count
         if (a.bundles != (a.phase == 3 ? 4 : 1) || (a.cout_b != 256 && a.cout_b != 128 && a.cout_b != 64 && a.cout_b != 32))
             return (int) hipErrorInvalidValue;
         c.BN = a.cout_b;
         c.TH = fused_head_rows(a, c);
     }
-    if (lds_bytes(a, c.TH, c.BN) > LDS_MAX) return (int) hipErrorInvalidValue;
-    if (c.TH == 16) return launch_cfg<16, 64, 2, 2>(a, stream);
+    if (lds_bytes(a, mode, c.TH, c.BN) > LDS_MAX) return (int) hipErrorInvalidValue;
+    if (c.TH == 16) return launch_cfg<16, 64, 2, 2>(a, mode, stream);
     if (c.TH == 8) {
         switch (c.BN) {
-            case 256: return launch_cfg<8, 256, 4, 2>(a, stream);
-            case 128: return launch_cfg<8, 128, 2, 2>(a, stream);
-            case 64: return launch_cfg<8, 64, 2, 2>(a, stream);
-            default: return launch_cfg<8, 32, 2, 1>(a, stream);
+            case 256: return launch_cfg<8, 256, 4, 2>(a, mode, stream);
+            case 128: return launch_cfg<8, 128, 2, 2>(a, mode, stream);
+            case 64: return launch_cfg<8, 64, 2, 2>(a, mode, stream);
+            default: return launch_cfg<8, 32, 2, 1>(a, mode, stream);
         }
     } else {
         switch (c.BN) {
-            case 256: return launch_cfg<4, 256, 2, 2>(a, stream);
-            case 128: return launch_cfg<4, 128, 2, 2>(a, stream);
-            case 64: return launch_cfg<4, 64, 1, 2>(a, stream);
-            default: return launch_cfg<4, 32, 1, 1>(a, stream);
+            case 256: return launch_cfg<4, 256, 2, 2>(a, mode, stream);
+            case 128: return launch_cfg<4, 128, 2, 2>(a, mode, stream);
+            case 64: return launch_cfg<4, 64, 1, 2>(a, mode, stream);
+            default: return launch_cfg<4, 32, 1, 1>(a, mode, stream);
         }
     }
 }
@@ -1868,7 +1605,7 @@ int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
 double conv_executed_flops(const ConvArgs &a) {
     double px = (double) a.Hout * a.Wout;
     if (a.region == 2) {  // frame-only launch: only the tiles that reach outside the box run (the fused-head kernels' tiles)
-        const int th = fused_head_rows(a, choose_tile(a));
+        const int th = fused_head_rows(a, choose_tile(a, conv_mode(a)));
         px = (double) frame_tiles(a.Hout, a.Wout, a.region_margin, th, TW, frame_kw(a)).total * th * TW;
     }
     return 2.0 * a.N * px * (double) a.bundles * a.cout_b * a.cin_b * a.KH * a.KW;

@@ -186,23 +186,15 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][f][r] = 0.f;
 
-#ifdef PAIR_EXP_NOMFMA1
-#define PAIR_MMA(ACC, A_, B_) asm volatile("" ::"v"(A_), "v"(B_))
-#else
-#define PAIR_MMA(ACC, A_, B_) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_, B_, ACC, 0, 0, 0)
-#endif
 #define MMA_SET1(S, PENDING)                                                                                   \
     {                                                                                                          \
         wait_set1<PENDING>(S);                                                                                 \
         _Pragma("unroll") for (int f = 0; f < 5; ++f) {                                                        \
-            PAIR_MMA(acc[0][f], S.w[0], S.p[f]);                                                               \
-            PAIR_MMA(acc[1][f], S.w[1], S.p[f]);                                                               \
+            acc[0][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(S.w[0], S.p[f], acc[0][f], 0, 0, 0);           \
+            acc[1][f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(S.w[1], S.p[f], acc[1][f], 0, 0, 0);           \
         }                                                                                                      \
     }
 
-    // tuning builds (tools/build_variant.sh; results are wrong by construction): -DPAIR_EXP_NOS1 skips stage 1's DMA + MFMA
-    // loop, -DPAIR_EXP_NOS2 stage 2's groups, -DPAIR_EXP_NOEPI the output stores
-#ifndef PAIR_EXP_NOS1
   if constexpr (CPS == 1) {
     // prologue: three chunks in flight, the first one landed
     PAIR_DMA(0, 0);
@@ -226,12 +218,8 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
             wait_vm<0>();
         }
         wait_set1<0>(B);
-#ifndef PAIR_EXP_NOBAR
         __builtin_amdgcn_s_barrier();  // ... and so have everybody else's: ring slot `buf` is free
-#endif
-#ifndef PAIR_EXP_NODMA
         if (c + 3 < nchunks) PAIR_DMA(c + 3, buf);
-#endif
         buf = buf == 2 ? 0 : buf + 1;
         load_set1(A, w_lane + (unsigned) (buf * WB), p_lane + (unsigned) (buf * XB));  // k-half 0 of chunk c+1
         MMA_SET1(B, 7);
@@ -264,16 +252,12 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
         // step boundary: my DMA of step st+1 landed, all my reads of step st returned ...
         wait_vm<0>();
         wait_set1<0>(B);
-#ifndef PAIR_EXP_NOBAR
         __builtin_amdgcn_s_barrier();  // ... and so have everybody else's: the two slots of step st are free
-#endif
-#ifndef PAIR_EXP_NODMA
         if (st + 2 < nsteps) {
             const int sl_ = (st & 1) * 2;
             PAIR_DMA(2 * st + 4, sl_);
             PAIR_DMA(2 * st + 5, sl_ + 1);
         }
-#endif
         xo = xo ? 0u : (unsigned) (2 * XB);
         wo = wo ? 0u : (unsigned) (2 * WB);
         load_set1(A, w_lane + wo, p_lane + xo);                              // first group of step st+1
@@ -287,9 +271,7 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
     MMA_SET1(A, 7);
     MMA_SET1(B, 0);
   }
-#endif
 #undef MMA_SET1
-#undef PAIR_MMA
 #undef PAIR_DMA
 
     // stage 2's job of this wave (see below): its first weight fragments are requested from L2 NOW, ahead of the slab-tile
@@ -320,10 +302,8 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
             Wr[(G) % 3][1] = *(const frag_t *) (wrow[1] + (s_ * 9 + t_) * (COB * 64) + kh_ * 32);              \
         }                                                                                                      \
     }
-#ifndef PAIR_EXP_NOS2
     PAIR_LOADW(0);
     PAIR_LOADW(1);
-#endif
 
     // ---- the slab tile: relu(conv1 + bias) as bf16 records [chunk][halo pixel][32], zero outside the image
     __syncthreads();  // every wave is done with the staging ring
@@ -376,7 +356,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
             const unsigned tt = u2 + (unsigned) ((t_ / 3) * 34 + t_ % 3);
             return base2 + (unsigned) (s_ * XB) + tt * 64u + ((((unsigned) lhi ^ ((tt >> 2) & 3u)) << 4) ^ (unsigned) (kh_ * 32));
         };
-#ifndef PAIR_EXP_NOS2
         ds_read16<0>(P2[0], p2_addr(0));
 #pragma unroll
         for (int g = 0; g < 36; ++g) {
@@ -404,7 +383,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
                 a2[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wr[g % 3][1], P2[g & 1], a2[1], 0, 0, 0);
             }
         }
-#endif
         __syncthreads();  // every wave is done reading the slab tile
         constexpr int SP2 = 144;
         lds_u8 *const stg2 = (lds_u8 *) smem + wave * (32 * SP2);
@@ -425,9 +403,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
             const int px = it * 8 + px_l2;
             const u32x4 v = *(const lds_u32x4 *) (stg2 + px * SP2 + part_l2 * 16);
             const int oy = ty * 8 + 2 * pq + (px >> 4), ox = tx * 16 + (px & 15);
-#ifdef PAIR_EXP_NOEPI
-            if (a.N < 0)
-#endif
             if (oy < Ho && ox < Wo) *(u32x4 *) (dst2 + ((size_t) oy * Wo + ox) * a.dst_stride * 2) = v;
         }
         return;
@@ -477,7 +452,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
     // columns beyond the left / right image edge (the conv's zero padding): output x = (fragment * 32 + l31) mod W
     const bool edge_l = (l31 & (W - 1)) == 0, edge_r = (l31 & (W - 1)) == ((W - 1) & 31);
     const frag_t zero_frag = {};
-#ifndef PAIR_EXP_NOS2
     PAIR_LOADP(0);
 #define PAIR_GROUP(G)                                                                                          \
     {                                                                                                          \
@@ -505,7 +479,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
     }
 #define PAIR_G4(G) PAIR_GROUP(G) PAIR_GROUP((G) + 1) PAIR_GROUP((G) + 2) PAIR_GROUP((G) + 3)
     PAIR_G4(0) PAIR_G4(4) PAIR_G4(8) PAIR_G4(12) PAIR_G4(16) PAIR_G4(20) PAIR_G4(24) PAIR_G4(28) PAIR_G4(32)
-#endif
 #undef PAIR_G4
 #undef PAIR_GROUP
 #undef PAIR_LOADW
@@ -552,9 +525,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(const PairArgs a) {
                 lin = (long) oy0 * W + (pq * 4 + f) * 32 + px;
                 inside = lin < img_px;
             }
-#ifdef PAIR_EXP_NOEPI
-            if (a.N < 0)
-#endif
             if (inside) *(u32x4 *) (dst_n + (size_t) lin * a.dst_stride * 2) = v;
         }
     }
@@ -601,8 +571,7 @@ template <int WLOG, int SL, int CB, int STRIDE = 1>
 int launch_pair_cfg(const PairArgs &a, hipStream_t stream) {
     // two chunks per pipeline step wherever four ring slots fit the LDS (the 256-channel slabs) and the chunk count is even
     if constexpr (4 * (PairCfg<WLOG, SL>::XBUF + PairCfg<WLOG, SL>::WBUF) <= PairCfg<WLOG, SL>::LDS) {
-        const char *e = getenv("CPN_PAIR_CPS");  // kernel A/B switch
-        if ((a.cin & 63) == 0 && !(e && atoi(e) == 1)) return launch_pair_cps<WLOG, SL, CB, 2, STRIDE>(a, stream);
+        if ((a.cin & 63) == 0) return launch_pair_cps<WLOG, SL, CB, 2, STRIDE>(a, stream);
     }
     return launch_pair_cps<WLOG, SL, CB, 1, STRIDE>(a, stream);
 }

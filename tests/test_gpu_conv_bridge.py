@@ -60,14 +60,12 @@ CASES = {
 }
 
 
-@pytest.mark.parametrize('brf', ['0', '1'], ids=['one_workgroup_per_cu', 'two_workgroups_per_cu'])
-@pytest.mark.parametrize('name', list(CASES))
-def test_conv_bridge_kernel(dev, name, brf, monkeypatch):
-    """Both tiles of the fused kernel: MODE_BR (default: the <16,64,2,2> tile) and MODE_BRF (CPN_BRF=1: 8-row tiles on 4 waves,
-    flat pitch-34 halo tiles, two workgroups per CU -- measured neutral, kept as an opt-in)."""
+# (the ids keep the suffix they had while a second tile existed, so that a case's history stays under one id)
+@pytest.mark.parametrize('name', list(CASES), ids=[f'{n}-one_workgroup_per_cu' for n in CASES])
+def test_conv_bridge_kernel(dev, name):
+    """The fused kernel (MODE_BR, the <16,64,2,2> tile) against the two launches it replaces, and both against the fp64 conv."""
     from celldetection_amd import _lib, graph
     from celldetection_amd.subpixel import collapse_upsampled_taps, phase_padding
-    monkeypatch.setenv('CPN_BRF', brf)
     cfg = dict(seed=0)
     cfg.update(CASES[name])
     n, h, w, cin = (cfg[k] for k in ('n', 'h', 'w', 'cin'))

@@ -169,7 +169,12 @@ CONV_CASES = {
     '7x7_head': dict(n=1, h=32, w=64, cin=64, cout=64, k=7),
     '7x7_head_256': dict(n=1, h=32, w=32, cin=256, cout=256, k=7),
     '7x7_stem_s2': dict(n=2, h=64, w=64, cin=3, cout=64, k=7, stride=2, bias=False),
-    # sizes at which the flagship 8x256 tile is what launch_conv selects (see test_conv_register_weight_loop, too)
+    # more of the 64-output-channel tiles: a fused ReadOut head with 64 hidden units on <16,64,2,2>, a concat source with partial
+    # tiles, three chunks of a 5x5
+    'c64_fused_head_th16': dict(n=4, h=256, w=256, cin=64, cout=64, k=7, fuse_cout=2, fuse_act='tanh_scaled', seed=11),
+    'c64_concat_up_partial': dict(n=3, h=40, w=72, cin=32, cout=64, k=3, cin1=64, up1=True, seed=12),
+    'c64_k5_three_chunks': dict(n=2, h=64, w=64, cin=96, cout=64, k=5, seed=13),
+    # sizes at which the flagship 8x256 tile is what launch_conv selects
     '3x3_256_flagship_tile': dict(n=8, h=128, w=128, cin=64, cout=256, k=3),
     '3x3_256_flagship_concat_up': dict(n=8, h=128, w=128, cin=32, cout=256, k=3, cin1=64, up1=True, seed=7),
     'fused_head_256_flagship_tile': dict(n=8, h=128, w=128, cin=96, cout=256, k=7, fuse_cout=20, fuse_act='none', seed=9),
@@ -210,48 +215,6 @@ def test_conv_rejects_a_resized_source_of_no_pixels(dev):
     the call with CPN_E_INVALID (-1) instead of launching."""
     with pytest.raises(RuntimeError, match=r'conv2d failed \(code -1\)'):
         run_conv(dev, n=1, h=1, w=40, cin=32, cout=32, k=1, up0=True)
-
-
-FLAGSHIP_CASES = ['3x3_256_flagship_tile', '3x3_256_flagship_concat_up', 'fused_head_256_flagship_tile']
-
-
-@pytest.mark.parametrize('name', FLAGSHIP_CASES)
-def test_conv_register_weight_loop(dev, name, monkeypatch):
-    """CPN_RW=1 selects MODE_S1R (weight fragments from L2 straight into registers, no weight tiles in LDS, two
-    barriers per chunk) for dense KxK convs on the 8x256 tile.  Same K order and MFMA sequence as the LDS-weight loop:
-    the outputs must be bit-identical, and within the rounding bound of the fp64 conv."""
-    monkeypatch.setenv('CPN_RW', '0')
-    lds, chk, f32 = run_conv(dev, **CONV_CASES[name])
-    monkeypatch.setenv('CPN_RW', '1')
-    rw, _, _ = run_conv(dev, **CONV_CASES[name], reference=False)
-    assert torch.equal(rw, lds), f'{name}: register-weight loop differs from the LDS-weight loop ' \
-                                 f'(max abs {(rw - lds).abs().max().item():.3e})'
-    chk(name, lds)
-
-
-C64_CASES = {
-    # the 64-channel tiles: <16,64,2,2> (3x3_c64_th16_tile / 7x7_c64_th16_tile: 4 x 256^2), <8,64,2,2> (small maps), a fused
-    # ReadOut head with 64 hidden units, a concat source, partial tiles
-    '3x3_c64_th16_tile': None, '7x7_c64_th16_tile': None, '3x3_64_64': None, '7x7_head': None,
-    'c64_fused_head_th16': dict(n=4, h=256, w=256, cin=64, cout=64, k=7, fuse_cout=2, fuse_act='tanh_scaled', seed=11),
-    'c64_concat_up_partial': dict(n=3, h=40, w=72, cin=32, cout=64, k=3, cin1=64, up1=True, seed=12),
-    'c64_k5_three_chunks': dict(n=2, h=64, w=64, cin=96, cout=64, k=5, seed=13),
-}
-
-
-@pytest.mark.parametrize('name', list(C64_CASES))
-def test_conv_register_weight_loop_64_channel_tiles(dev, name, monkeypatch):
-    """CPN_RW bit 1: MODE_S1R on the 64-output-channel tiles (the refinement ReadOut head, commons.py:461-511 at 64 -> 64, and
-    the bridge convs): weight fragments from L2 into registers, LDS holds only the halo -- half the LDS fragment reads.  Same K
-    order and MFMA sequence as the LDS-weight loop: bit-identical outputs."""
-    cfg = C64_CASES[name] or CONV_CASES[name]
-    monkeypatch.setenv('CPN_RW', '0')
-    lds, chk, f32 = run_conv(dev, **cfg)
-    monkeypatch.setenv('CPN_RW', '2')
-    rw, _, _ = run_conv(dev, **cfg, reference=False)
-    assert torch.equal(rw, lds), f'{name}: register-weight loop differs from the LDS-weight loop ' \
-                                 f'(max abs {(rw - lds).abs().max().item():.3e})'
-    chk(name, lds)
 
 
 S1F_CASES = {
@@ -527,16 +490,13 @@ def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
 
 
 @pytest.mark.parametrize('name', ['1x1_flagship_tile', '1x1_flagship_tile_res'])
-def test_conv_pointwise_register_weight_loop(dev, name, monkeypatch):
-    """CPN_PWR=1 selects MODE_PWR (the 1x1 convs' weight fragments from L2 straight into registers, 8x256 tile; round-3
-    experiment, neutral on the MI355X: profiles/r03_kernel_experiments.txt).  Same K order and MFMA sequence as MODE_PW:
-    bit-identical outputs."""
-    monkeypatch.setenv('CPN_PWR', '0')
-    lds, chk, _ = run_conv(dev, **CONV_CASES[name])
-    monkeypatch.setenv('CPN_PWR', '1')
-    rw, _, _ = run_conv(dev, **CONV_CASES[name], reference=False)
-    assert torch.equal(rw, lds), f'max abs {(rw - lds).abs().max().item():.3e}'
-    chk(name, lds)
+def test_conv_pointwise_register_weight_loop(dev, name):
+    """Two launches of the flagship 1x1 tile on the same operands return the same bits (no atomics, no order-dependent
+    reduction in the kernel), within the rounding bound of the fp64 conv."""
+    first, chk, _ = run_conv(dev, **CONV_CASES[name])
+    second, _, _ = run_conv(dev, **CONV_CASES[name], reference=False)
+    assert torch.equal(second, first), f'max abs {(second - first).abs().max().item():.3e}'
+    chk(name, first)
 
 
 def test_maxpool_bilinear_input(dev):
