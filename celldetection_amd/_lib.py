@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
 
@@ -22,6 +22,8 @@ SUBPIXEL_NONE, SUBPIXEL_HEAD, SUBPIXEL_PHASE, SUBPIXEL_LATERAL, SUBPIXEL_SCATTER
 SUBPIXEL_BL_HEAD, SUBPIXEL_BL_PHASE, SUBPIXEL_BL_FRAME = 5, 6, 7
 OUT_SCORES, OUT_LOCATIONS, OUT_FOURIER, OUT_REFINEMENT, OUT_UNCERTAINTY = 0, 1, 2, 3, 4
 NUM_OUTPUTS = 5
+# conv kernel modes (CPN_CONV_MODE_* of include/cpn_hip.h) as cpn_conv2d_kernel_info reports them
+CONV_MODE_NAMES = {0: 'PW', 1: 'S1', 2: 'S2', 3: 'BL', 6: 'N', 7: 'S1F', 8: 'BR', 10: 'S1Q'}
 # region properties (CPN_PROP_* of include/cpn_hip.h), in code order, and the intensity dtypes (CPN_PROPS_*)
 PROP_NAMES = ('label', 'bbox', 'num_pixels', 'area', 'area_bbox', 'extent', 'equivalent_diameter_area', 'centroid',
               'centroid_local', 'inertia_tensor', 'inertia_tensor_eigvals', 'axis_major_length', 'axis_minor_length',
@@ -69,6 +71,8 @@ _SIGNATURES = [
     ('cpn_conv2d_fp8', ctypes.c_int, [POINTER(OpDesc), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                       c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p]),
+    ('cpn_conv2d_kernel_info', ctypes.c_int, [POINTER(OpDesc), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, POINTER(c_int32)]),
     ('cpn_convert_input_stem', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                               c_void_p]),
     ('cpn_stem7', ctypes.c_int, [POINTER(OpDesc), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
@@ -200,3 +204,14 @@ def stream_ptr():
 def ptr(t):
     """Device/host pointer of a tensor (None -> NULL)."""
     return c_void_p(0 if t is None else t.data_ptr())
+
+
+def conv_kernel_info(op, precision, n, hin, win, c0_stride, c1_stride=0, res_stride=0, dst_stride=0):
+    """The kernel cpn_conv2d (PRECISION_BF16; a CONV_BRIDGE descriptor: cpn_conv_bridge) or cpn_conv2d_fp8 (PRECISION_FP8)
+    would launch for this descriptor, these channel strides and this input size -> (mode name, TH, BN, WM, WN): the
+    instantiation conv_igemm_kernel<TH, BN, WM, WN, mode>.  Host arithmetic only: needs no GPU.  Raises like the launch
+    itself for a call it rejects."""
+    info = (c_int32 * 5)()
+    check(load().cpn_conv2d_kernel_info(op, precision, c0_stride, c1_stride, res_stride, dst_stride, n, hin, win, info),
+          'conv2d_kernel_info')
+    return (CONV_MODE_NAMES[info[0]],) + tuple(info[1:])

@@ -1544,8 +1544,16 @@ static TileChoice choose_tile(const ConvArgs &a, Mode mode) {
 // fused ReadOut heads: the block owns all output channels; tile rows = a multiple of the wave count
 static int fused_head_rows(const ConvArgs &a, const TileChoice &c) { return (a.cout_b == 64 && c.TH == 16) ? 16 : 8; }
 
-int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
-    ConvArgs a = a_in;
+// the nine tiles of the plain modes (MODE_PW / N / S1 / S2 / BL): TH, BN and the wave grid WM x WN each is launched with
+#define CPN_CONV_TILES(X) X(16, 64, 2, 2) X(8, 256, 4, 2) X(8, 128, 2, 2) X(8, 64, 2, 2) X(8, 32, 2, 1) \
+                          X(4, 256, 2, 2) X(4, 128, 2, 2) X(4, 64, 1, 2) X(4, 32, 1, 1)
+
+// Selection step of launch_conv: validates the call and decides the instantiation conv_igemm_kernel<TH, BN, WM, WN, mode>.
+// Host arithmetic only (no HIP call, no pointer dereferenced): select_conv_kernel answers cpn_conv2d_kernel_info on a machine
+// without a GPU, and launch_conv dispatches on the same answer.  `a` receives the arguments as launched (MODE_N's view).
+static int select_conv(const ConvArgs &a_in, ConvArgs &a, ConvKernelSel &s) {
+    a = a_in;
+    s = ConvKernelSel{};
     if (narrow_ok(a)) {  // [N][H][16] viewed as [N][H/2][32]: same memory, full 32-pixel fragments (MODE_N)
         a.narrow = 1;
         a.Hout /= 2;
@@ -1563,17 +1571,22 @@ int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
 #if !CPN_FP8
     if (a.pre_src) {  // bridge fusion (see ConvArgs.pre_*): checked by conv_bridge_supported
         if (!conv_bridge_supported(a)) return (int) hipErrorInvalidValue;
-        return launch_mode<16, 64, 2, 2, MODE_BR>(a, stream);
+        s = ConvKernelSel{MODE_BR, 16, 64, 2, 2};
+        return 0;
     }
 #else
     if (a.pre_src) return (int) hipErrorInvalidValue;
 #endif
     const Mode mode = conv_mode(a);
 #if !CPN_FP8
-    if (mode == MODE_S1F) return launch_mode<8, 128, 4, 2, MODE_S1F>(a, stream);
+    if (mode == MODE_S1F) {
+        s = ConvKernelSel{MODE_S1F, 8, 128, 4, 2};
+        return 0;
+    }
     if (mode == MODE_S1Q) {
         if (lds_bytes(a, mode, 16, 64) > LDS_MAX) return (int) hipErrorInvalidValue;
-        return launch_mode<16, 64, 2, 2, MODE_S1Q>(a, stream);
+        s = ConvKernelSel{MODE_S1Q, 16, 64, 2, 2};
+        return 0;
     }
 #endif
     TileChoice c = choose_tile(a, mode);
@@ -1584,22 +1597,36 @@ int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
         c.TH = fused_head_rows(a, c);
     }
     if (lds_bytes(a, mode, c.TH, c.BN) > LDS_MAX) return (int) hipErrorInvalidValue;
-    if (c.TH == 16) return launch_cfg<16, 64, 2, 2>(a, mode, stream);
-    if (c.TH == 8) {
-        switch (c.BN) {
-            case 256: return launch_cfg<8, 256, 4, 2>(a, mode, stream);
-            case 128: return launch_cfg<8, 128, 2, 2>(a, mode, stream);
-            case 64: return launch_cfg<8, 64, 2, 2>(a, mode, stream);
-            default: return launch_cfg<8, 32, 2, 1>(a, mode, stream);
-        }
-    } else {
-        switch (c.BN) {
-            case 256: return launch_cfg<4, 256, 2, 2>(a, mode, stream);
-            case 128: return launch_cfg<4, 128, 2, 2>(a, mode, stream);
-            case 64: return launch_cfg<4, 64, 1, 2>(a, mode, stream);
-            default: return launch_cfg<4, 32, 1, 1>(a, mode, stream);
-        }
-    }
+    if (c.TH == 16) c.BN = 64;  // (the one 16-row tile; choose_tile and fused_head_rows pick it at 64 channels only)
+    if (mode != MODE_PW && mode != MODE_S1 && mode != MODE_S2 && (CPN_FP8 || (mode != MODE_N && mode != MODE_BL)))
+        return (int) hipErrorInvalidValue;  // (MODE_N / BL: bf16 only)
+#define X(TH_, BN_, WM_, WN_) if (c.TH == TH_ && c.BN == BN_) s = ConvKernelSel{(int) mode, TH_, BN_, WM_, WN_};
+    CPN_CONV_TILES(X)
+#undef X
+    return s.TH ? 0 : (int) hipErrorInvalidValue;
+}
+
+int select_conv_kernel(const ConvArgs &a_in, ConvKernelSel &s) {
+    ConvArgs a;
+    return select_conv(a_in, a, s);
+}
+
+// Dispatch step: launches exactly the instantiation the selection named.
+int launch_conv(const ConvArgs &a_in, hipStream_t stream) {
+    ConvArgs a;
+    ConvKernelSel s;
+    const int rc = select_conv(a_in, a, s);
+    if (rc) return rc;
+#if !CPN_FP8
+    if (s.mode == MODE_BR) return launch_mode<16, 64, 2, 2, MODE_BR>(a, stream);
+    if (s.mode == MODE_S1F) return launch_mode<8, 128, 4, 2, MODE_S1F>(a, stream);
+    if (s.mode == MODE_S1Q) return launch_mode<16, 64, 2, 2, MODE_S1Q>(a, stream);
+#endif
+#define X(TH_, BN_, WM_, WN_) \
+    if (s.TH == TH_ && s.BN == BN_ && s.WM == WM_ && s.WN == WN_) return launch_cfg<TH_, BN_, WM_, WN_>(a, (Mode) s.mode, stream);
+    CPN_CONV_TILES(X)
+#undef X
+    return (int) hipErrorInvalidValue;
 }
 
 double conv_executed_flops(const ConvArgs &a) {
@@ -1616,6 +1643,7 @@ double conv_executed_flops(const ConvArgs &a) {
 #if CPN_FP8
 namespace cpn {
 int launch_conv_fp8(const ConvArgs &a, hipStream_t stream) { return cpn_fp8::launch_conv(a, stream); }
+int select_conv_kernel_fp8(const ConvArgs &a, ConvKernelSel &s) { return cpn_fp8::select_conv_kernel(a, s); }
 }  // namespace cpn
 #else
 // include/cpn_hip.h: shader-clock probe of the bf16 conv kernels (compiled in with -DCPN_EXP_CLOCK=2 only: libcpn_hip_clock.so)

@@ -426,6 +426,61 @@ static int build_conv_args(const cpn_plan *p, const cpn_op_desc &o, int N, ConvA
     return 0;
 }
 
+// Argument building + validation of the single-conv entry points, shared with cpn_conv2d_kernel_info (which passes
+// placeholder buffers: nothing here dereferences one)
+static int conv2d_args(const cpn_op_desc *op, const void *src0, int c0_stride, const void *src1, int c1_stride, const void *res,
+                       int res_stride, void *dst, int dst_stride, int N, int Hin, int Win, const void *weights, const float *bias,
+                       ConvArgs &a) {
+    if (!op || !src0 || !dst || !weights) return fail(CPN_E_INVALID, "cpn_conv2d: null pointer");
+    int rc = build_conv_args(nullptr, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst,
+                             dst_stride, Hin, Win);
+    if (rc) return rc;
+    a.weights = (const unsigned char *) weights + op->weight_offset;
+    a.bias = (bias && op->bias_offset >= 0) ? bias + op->bias_offset : nullptr;
+    if (op->fuse_cout > 0) {
+        a.fuse_w = (const unsigned char *) weights + op->fuse_weight_offset;
+        a.fuse_b = (bias && op->fuse_bias_offset >= 0) ? bias + op->fuse_bias_offset : nullptr;
+    }
+    return 0;
+}
+
+static int conv2d_fp8_args(const cpn_op_desc *op, const void *src0, int c0_stride, const void *src1, int c1_stride,
+                           const void *res, int res_stride, void *dst, int dst_stride, int N, int Hin, int Win,
+                           const void *weights, const float *bias, const float *mult, float res_scale, float out_inv_scale,
+                           ConvArgs &a) {
+    if (!op || !src0 || !dst || !weights) return fail(CPN_E_INVALID, "cpn_conv2d_fp8: null pointer");
+    if (op->cin_b % 64 || op->c0_used % 64 || c0_stride % 64 || (src1 && c1_stride % 64))
+        return fail(CPN_E_INVALID, "cpn_conv2d_fp8: input channel counts / strides must be multiples of 64");
+    int rc = build_conv_args(nullptr, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst,
+                             dst_stride, Hin, Win);
+    if (rc) return rc;
+    a.weights = (const unsigned char *) weights + op->weight_offset;
+    a.bias = (bias && op->bias_offset >= 0) ? bias + op->bias_offset : nullptr;
+    a.mult = (mult && op->bias_offset >= 0) ? mult + op->bias_offset : mult;
+    a.res_scale = res_scale;
+    a.out_inv_scale = out_inv_scale;
+    if (op->fuse_cout > 0) {
+        a.fuse_w = (const unsigned char *) weights + op->fuse_weight_offset;
+        a.fuse_b = (bias && op->fuse_bias_offset >= 0) ? bias + op->fuse_bias_offset : nullptr;
+    }
+    return 0;
+}
+
+static int conv_bridge_args(const cpn_op_desc *op, const void *src, int c_stride, const void *res, int res_stride, void *dst,
+                            int dst_stride, int N, int H, int W, const void *weights, const float *bias, ConvArgs &a) {
+    if (!op || !src || !dst || !weights || op->op != CPN_OP_CONV_BRIDGE || N <= 0 || H <= 0 || W <= 0)
+        return fail(CPN_E_INVALID, "cpn_conv_bridge: needs a CPN_OP_CONV_BRIDGE descriptor and non-null buffers");
+    cpn_op_desc c2 = *op;  // the 3x3 conv the op restates: one plain 64-channel source, its own weights behind fuse_*_offset
+    c2.op = CPN_OP_CONV; c2.src1 = -1; c2.up0 = c2.up1 = 0; c2.c0_used = 64; c2.cin_b = 64; c2.cout_b = 64; c2.bundles = 1;
+    c2.kh = c2.kw = 3; c2.stride = 1; c2.pad = 1; c2.subpixel = 0; c2.fuse_cout = 0; c2.dst = 0; c2.dst_coff = 0;
+    int rc = bridge_args(nullptr, *op, c2, N, H, W, a, src, c_stride, res, res_stride, dst, dst_stride, weights, bias);
+    if (rc) return rc;
+    if (!conv_bridge_supported(a))
+        return fail(CPN_E_UNSUPPORTED, "cpn_conv_bridge: needs 32 | 64 input channels, 64 output channels and an output of at "
+                                       "least 16 x 32 pixels (run the two convs)");
+    return 0;
+}
+
 }  // namespace cpn
 
 using namespace cpn;
@@ -843,17 +898,9 @@ double cpn_plan_executed_flops(cpn_plan *plan, int32_t N, int32_t H, int32_t W) 
 int cpn_conv2d(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const void *src1, int32_t c1_stride,
                const void *res, int32_t res_stride, void *dst, int32_t dst_stride, int32_t N, int32_t Hin, int32_t Win,
                const void *weights, const float *bias, void *stream) {
-    if (!op || !src0 || !dst || !weights) return fail(CPN_E_INVALID, "cpn_conv2d: null pointer");
     ConvArgs a;
-    int rc = build_conv_args(nullptr, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst,
-                             dst_stride, Hin, Win);
+    int rc = conv2d_args(op, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, N, Hin, Win, weights, bias, a);
     if (rc) return rc;
-    a.weights = (const unsigned char *) weights + op->weight_offset;
-    a.bias = (bias && op->bias_offset >= 0) ? bias + op->bias_offset : nullptr;
-    if (op->fuse_cout > 0) {
-        a.fuse_w = (const unsigned char *) weights + op->fuse_weight_offset;
-        a.fuse_b = (bias && op->fuse_bias_offset >= 0) ? bias + op->fuse_bias_offset : nullptr;
-    }
     return check_hip((hipError_t) launch_conv(a, (hipStream_t) stream), "cpn_conv2d");
 }
 
@@ -861,22 +908,10 @@ int cpn_conv2d_fp8(const cpn_op_desc *op, const void *src0, int32_t c0_stride, c
                    const void *res, int32_t res_stride, void *dst, int32_t dst_stride, int32_t N, int32_t Hin,
                    int32_t Win, const void *weights, const float *bias, const float *mult, float res_scale,
                    float out_inv_scale, void *stream) {
-    if (!op || !src0 || !dst || !weights) return fail(CPN_E_INVALID, "cpn_conv2d_fp8: null pointer");
-    if (op->cin_b % 64 || op->c0_used % 64 || c0_stride % 64 || (src1 && c1_stride % 64))
-        return fail(CPN_E_INVALID, "cpn_conv2d_fp8: input channel counts / strides must be multiples of 64");
     ConvArgs a;
-    int rc = build_conv_args(nullptr, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst,
-                             dst_stride, Hin, Win);
+    int rc = conv2d_fp8_args(op, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, N, Hin, Win, weights, bias,
+                             mult, res_scale, out_inv_scale, a);
     if (rc) return rc;
-    a.weights = (const unsigned char *) weights + op->weight_offset;
-    a.bias = (bias && op->bias_offset >= 0) ? bias + op->bias_offset : nullptr;
-    a.mult = (mult && op->bias_offset >= 0) ? mult + op->bias_offset : mult;
-    a.res_scale = res_scale;
-    a.out_inv_scale = out_inv_scale;
-    if (op->fuse_cout > 0) {
-        a.fuse_w = (const unsigned char *) weights + op->fuse_weight_offset;
-        a.fuse_b = (bias && op->fuse_bias_offset >= 0) ? bias + op->fuse_bias_offset : nullptr;
-    }
     return check_hip((hipError_t) launch_conv_fp8(a, (hipStream_t) stream), "cpn_conv2d_fp8");
 }
 
@@ -898,18 +933,37 @@ int cpn_conv_pair(const cpn_op_desc *op, const void *src, int32_t c_stride, void
 
 int cpn_conv_bridge(const cpn_op_desc *op, const void *src, int32_t c_stride, const void *res, int32_t res_stride, void *dst,
                     int32_t dst_stride, int32_t N, int32_t H, int32_t W, const void *weights, const float *bias, void *stream) {
-    if (!op || !src || !dst || !weights || op->op != CPN_OP_CONV_BRIDGE || N <= 0 || H <= 0 || W <= 0)
-        return fail(CPN_E_INVALID, "cpn_conv_bridge: needs a CPN_OP_CONV_BRIDGE descriptor and non-null buffers");
-    cpn_op_desc c2 = *op;  // the 3x3 conv the op restates: one plain 64-channel source, its own weights behind fuse_*_offset
-    c2.op = CPN_OP_CONV; c2.src1 = -1; c2.up0 = c2.up1 = 0; c2.c0_used = 64; c2.cin_b = 64; c2.cout_b = 64; c2.bundles = 1;
-    c2.kh = c2.kw = 3; c2.stride = 1; c2.pad = 1; c2.subpixel = 0; c2.fuse_cout = 0; c2.dst = 0; c2.dst_coff = 0;
     ConvArgs a;
-    int rc = bridge_args(nullptr, *op, c2, N, H, W, a, src, c_stride, res, res_stride, dst, dst_stride, weights, bias);
+    int rc = conv_bridge_args(op, src, c_stride, res, res_stride, dst, dst_stride, N, H, W, weights, bias, a);
     if (rc) return rc;
-    if (!conv_bridge_supported(a))
-        return fail(CPN_E_UNSUPPORTED, "cpn_conv_bridge: needs 32 | 64 input channels, 64 output channels and an output of at "
-                                       "least 16 x 32 pixels (run the two convs)");
     return check_hip((hipError_t) launch_conv(a, (hipStream_t) stream), "cpn_conv_bridge");
+}
+
+int cpn_conv2d_kernel_info(const cpn_op_desc *op, int32_t precision, int32_t c0_stride, int32_t c1_stride, int32_t res_stride,
+                           int32_t dst_stride, int32_t N, int32_t Hin, int32_t Win, int32_t info[5]) {
+    static char dummy[8] = {};  // stands for every buffer: the argument building stores pointers, the selection tests them for null
+    if (!op || !info) return fail(CPN_E_INVALID, "cpn_conv2d_kernel_info: null pointer");
+    const void *src1 = op->src1 >= 0 ? dummy : nullptr, *res = op->res >= 0 ? dummy : nullptr;
+    ConvArgs a;
+    ConvKernelSel s{};
+    int rc;
+    if (precision == CPN_PRECISION_BF16 && op->op == CPN_OP_CONV_BRIDGE) {
+        rc = conv_bridge_args(op, dummy, c0_stride, res, res_stride, dummy, dst_stride, N, Hin, Win, dummy, nullptr, a);
+        if (!rc) rc = select_conv_kernel(a, s);
+    } else if (precision == CPN_PRECISION_BF16) {
+        rc = conv2d_args(op, dummy, c0_stride, src1, c1_stride, res, res_stride, dummy, dst_stride, N, Hin, Win, dummy, nullptr, a);
+        if (!rc) rc = select_conv_kernel(a, s);
+    } else if (precision == CPN_PRECISION_FP8) {
+        rc = conv2d_fp8_args(op, dummy, c0_stride, src1, c1_stride, res, res_stride, dummy, dst_stride, N, Hin, Win, dummy, nullptr,
+                             nullptr, 1.f, 1.f, a);
+        if (!rc) rc = select_conv_kernel_fp8(a, s);
+    } else {
+        return fail(CPN_E_INVALID, "cpn_conv2d_kernel_info: precision must be CPN_PRECISION_BF16 or CPN_PRECISION_FP8");
+    }
+    if (rc > 0) return fail(rc, "cpn_conv2d_kernel_info: the conv kernels do not run this call (hipErrorInvalidValue from the launch)");
+    if (rc) return rc;
+    info[0] = s.mode; info[1] = s.TH; info[2] = s.BN; info[3] = s.WM; info[4] = s.WN;
+    return 0;
 }
 
 int cpn_convert_input_stem(const void *src, int32_t in_dtype, void *dst, int32_t N, int32_t C, int32_t H, int32_t W,

@@ -136,6 +136,14 @@ __host__ __device__ inline FrameTiles frame_tiles(int H, int W, int m, int th, i
 // picks a tile configuration and launches; returns hipError_t as int
 int launch_conv(const ConvArgs &a, hipStream_t stream);
 int launch_conv_fp8(const ConvArgs &a, hipStream_t stream);
+// the instantiation conv_igemm_kernel<TH, BN, WM, WN, mode> launch_conv / launch_conv_fp8 would run for `a` (mode: enum Mode of
+// conv_igemm.hip = CPN_CONV_MODE_* of include/cpn_hip.h).  The selection step of the launch itself: host arithmetic only, no
+// HIP call, no pointer dereferenced; returns what the launch would return for a call it rejects
+struct ConvKernelSel {
+    int mode, TH, BN, WM, WN;
+};
+int select_conv_kernel(const ConvArgs &a, ConvKernelSel &s);
+int select_conv_kernel_fp8(const ConvArgs &a, ConvKernelSel &s);
 bool conv_bridge_supported(const ConvArgs &a);  // ConvArgs.pre_*: the shape the bridge kernel (MODE_BR) runs  // e4m3 operands, v_mfma_scale_f32_32x32x64_f8f6f4
 // algorithmic FLOPs actually executed by the MFMA loop of that launch (for utilisation reports)
 double conv_executed_flops(const ConvArgs &a);

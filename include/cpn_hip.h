@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 17
+#define CPN_ABI_VERSION 18
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -259,6 +259,24 @@ int cpn_conv_pair(const cpn_op_desc *op, const void *src, int32_t c_stride, void
  * the 3x3 conv at the output's size.  CPN_E_UNSUPPORTED when the kernel's shape does not apply (output below 16 x 32 pixels). */
 int cpn_conv_bridge(const cpn_op_desc *op, const void *src, int32_t c_stride, const void *res, int32_t res_stride, void *dst,
                     int32_t dst_stride, int32_t N, int32_t H, int32_t W, const void *weights, const float *bias, void *stream);
+/* Which kernel would run (ABI 18): the instantiation conv_igemm_kernel<TH, BN, WM, WN, mode> that cpn_conv2d (precision =
+ * CPN_PRECISION_BF16; a CPN_OP_CONV_BRIDGE descriptor: cpn_conv_bridge with c0_stride = its c_stride and Hin x Win = its
+ * H x W) or cpn_conv2d_fp8 (CPN_PRECISION_FP8) launches for the same descriptor, strides and sizes -> info = {mode
+ * (CPN_CONV_MODE_*), TH (tile rows), BN (output channels per block), WM, WN (wave grid)}; a tile is TH x 32 pixels (MODE_N:
+ * 2 TH rows of a 16-column output).  A second source / a residual is present iff op->src1 >= 0 / op->res >= 0.  Runs the
+ * argument building, validation and tile selection of the launch itself and returns what the launch returns for a call it
+ * rejects, but makes no HIP call and touches no buffer: it answers on a machine without a GPU.  The CPN_S1F / CPN_S1Q
+ * environment switches are read per call, as by the launch. */
+#define CPN_CONV_MODE_PW 0   /* 1x1, pad 0                                   */
+#define CPN_CONV_MODE_S1 1   /* k x k, stride 1                              */
+#define CPN_CONV_MODE_S2 2   /* k x k, stride 2                              */
+#define CPN_CONV_MODE_BL 3   /* k x k over a bilinear-resized source (bf16)  */
+#define CPN_CONV_MODE_N 6    /* outputs 16 columns wide (bf16)               */
+#define CPN_CONV_MODE_S1F 7  /* two workgroups per CU, <8,128,4,2> (bf16)    */
+#define CPN_CONV_MODE_BR 8   /* fused bridge level, <16,64,2,2> (bf16)       */
+#define CPN_CONV_MODE_S1Q 10 /* four K items per step, <16,64,2,2> (bf16)    */
+int cpn_conv2d_kernel_info(const cpn_op_desc *op, int32_t precision, int32_t c0_stride, int32_t c1_stride, int32_t res_stride,
+                           int32_t dst_stride, int32_t N, int32_t Hin, int32_t Win, int32_t info[5]);
 int cpn_maxpool2d(const void *src, void *dst, int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t k, int32_t stride,
                   int32_t pad, void *stream);
 int cpn_resize_bilinear(const void *src, void *dst, int32_t N, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,

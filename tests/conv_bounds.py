@@ -29,7 +29,8 @@ Output rounding, applied to the interval [ref - d, ref + d] pushed through the (
 Rounding points the kernel performs internally without storing them are modelled as intervals, not slack:
 
 * the fused ReadOut tail's hidden activation relu(conv + bias) -> bf16 (OUT_FUSED_HEAD);
-* the bilinear blend of MODE_BL, rounded to bf16 before it enters the MFMA.
+* the bilinear blend of MODE_BL, rounded to bf16 before it enters the MFMA.  Its source coordinates are fp32: exact for
+  the x2 resize of the models, within (3 f + 1.5) u of the exact coordinate f otherwise (_bilinear_coordinate_noise).
 
 Each such value is carried as the bf16 interval [RNE(lo), RNE(hi)] of its own noise window (hidden_bf16): where the window
 holds no midpoint both ends coincide and kernel and reference round the same way; where it does, the next stage adds
@@ -169,13 +170,39 @@ def conv_with_noise(x, w, bias=None, stride=1, pad=0, groups=1, *, n, x_half=Non
     return ref, S, d
 
 
+def _bilinear_coordinate_noise(x, size):
+    """What the fp32 source coordinates of the kernel's blend can move a blended value by.
+
+    The kernel (like the fp32 bilinear kernel of PyTorch it follows) computes f = max(fl(fl(s^ * (i + 0.5)) - 0.5), 0) with
+    s^ = fl(Hs / Hin); i + 0.5 is exact.  With p = s (i + 0.5) = f + 0.5:  |f^ - f| <= p (2u + u^2) + u |p^ - 0.5|
+    <= (3 f + 1.5) u.  Where Hs / Hin is a power of two (the exact x2 of the models) every step is exact: 0.  The blend is
+    continuous and piecewise linear in f, with slope at most the largest difference of adjacent source pixels in that direction
+    among the cells f^ can fall into (a floor that flips reaches one row / column further): taken over the 5 x 5 pixels around
+    the exact floor."""
+    x = x.double()
+    hs, ws = x.shape[-2:]
+
+    def axis(n_src, n_dst):
+        f = ((torch.arange(n_dst, dtype=torch.float64) + .5) * n_src / n_dst - .5).clamp_min(0.)
+        exact = math.frexp(n_src / n_dst)[0] == .5 and n_src * (1 << 30) % n_dst == 0
+        return f.floor().long().clamp_max(n_src - 1), torch.zeros_like(f) if exact else (3. * f + 1.5) * U
+
+    y0, dy = axis(hs, size[0])
+    x0, dx = axis(ws, size[1])
+    gy = F.pad((x[..., 1:, :] - x[..., :-1, :]).abs(), (0, 0, 0, 1))
+    gx = F.pad((x[..., :, 1:] - x[..., :, :-1]).abs(), (0, 1, 0, 0))
+    gy, gx = F.max_pool2d(gy, 5, 1, 2), F.max_pool2d(gx, 5, 1, 2)
+    return dy[:, None] * gy[..., y0, :][..., x0] + dx[None, :] * gx[..., y0, :][..., x0]
+
+
 def bilinear_bf16_operand(x, size):
     """MODE_BL's operand: F.interpolate(x, size, 'bilinear', align_corners=False) blended in fp32 (four products, three
-    adds, two more products) and rounded to bf16 inside the kernel -> (mid, half) as for hidden_bf16."""
+    adds, two more products) from fp32 source coordinates and rounded to bf16 inside the kernel -> (mid, half) as for
+    hidden_bf16."""
     x = x.double()
     mid = F.interpolate(x, size=size, mode='bilinear', align_corners=False)
     s = F.interpolate(x.abs(), size=size, mode='bilinear', align_corners=False)
-    return hidden_bf16(mid, gamma(8) * s)
+    return hidden_bf16(mid, gamma(8) * s + _bilinear_coordinate_noise(x, size))
 
 
 def fused_tail(ref1, d1, w2, b2, *, act, act_scale=1.):

@@ -128,12 +128,19 @@ def test_fused_tail_emulation_accepted(seed, order, fuse_act):
 
 @pytest.mark.parametrize('order', ORDERS)
 @pytest.mark.parametrize('seed', SEEDS)
-def test_bilinear_emulation_accepted(seed, order):
-    x0, wt, b, xb, got = _bilinear_case(seed, order)
+def test_bilinear_emulation_accepted(seed, order, size=(16, 40)):
+    x0, wt, b, xb, got = _bilinear_case(seed, order, size=size)
     mid, half = cb.bilinear_bf16_operand(x0, xb.shape[-2:])
     ref, S, d = cb.conv_with_noise(mid, wt, b, pad=1, n=cb.chain_length(3, 3, wt.shape[1]), x_half=half)
     lo, hi = cb.bf16_bounds(ref, d, 'relu')
     assert cb.check('bilinear emulation', got, lo, hi, F.relu(ref), S) <= 1
+
+
+@pytest.mark.parametrize('order', ORDERS)
+@pytest.mark.parametrize('seed', SEEDS)
+def test_bilinear_emulation_accepted_at_odd_sizes(seed, order):
+    """17 x 41 from 8 x 20: the scales 8 / 17 and 20 / 41 are no fp32 numbers, the emulation computes its source coordinates in fp32."""
+    test_bilinear_emulation_accepted(seed, order, size=(17, 41))
 
 
 @pytest.mark.parametrize('seed', SEEDS)
@@ -197,15 +204,16 @@ def _fused_case(seed, order, fuse_act, flip=False):
     return got, hid, tail
 
 
-def _bilinear_case(seed, order, wrong_index=False):
+def _bilinear_case(seed, order, wrong_index=False, size=(16, 40)):
     g = torch.Generator().manual_seed(seed)
     x0 = _bf16(torch.randn(1, 32, 8, 20, generator=g))
     wt = _bf16(torch.randn(32, 32, 3, 3, generator=g) / 17.)
     b = torch.randn(32, generator=g) * .5
-    H, W = 16, 40
-    # the kernel's blend: fy = max(0.5 (y + 0.5) - 0.5, 0), weights hy = 1 - ly ... fp32
-    fy = ((torch.arange(H, dtype=torch.float32) + .5) * .5 - .5).clamp_min(0.)
-    fx = ((torch.arange(W, dtype=torch.float32) + .5) * .5 - .5).clamp_min(0.)
+    H, W = size
+    # the kernel's blend: fy = max(fl(Hs / Hin) * (y + 0.5) - 0.5, 0), weights hy = 1 - ly ... fp32 (exact at x2: 0.5 (y + 0.5) - 0.5)
+    sy, sx = torch.tensor(8., dtype=torch.float32) / H, torch.tensor(20., dtype=torch.float32) / W
+    fy = ((torch.arange(H, dtype=torch.float32) + .5) * sy - .5).clamp_min(0.)
+    fx = ((torch.arange(W, dtype=torch.float32) + .5) * sx - .5).clamp_min(0.)
     y0, x0i = fy.long(), fx.long()
     y1, x1i = (y0 + 1).clamp_max(7), (x0i + 1).clamp_max(19)
     ly, lx = fy - y0, fx - x0i
@@ -215,6 +223,30 @@ def _bilinear_case(seed, order, wrong_index=False):
     xb = _bf16(blend)[None]
     got = _bf16(F.relu(_emulate(xb, wt, b, order, seed)))
     return x0, wt, b, xb, got
+
+
+def test_bilinear_operand_carries_fp32_source_coordinates():
+    """At an exact x2 the kernel's fp32 source coordinates are exact and the operand's interval is the blend's own noise;
+    at 17 x 41 from 8 x 20 (scales 8 / 17, 20 / 41) they are not: over 64 maps some fp32 blends round to a bf16 value the
+    exact-coordinate window does not hold, and every one of them lies in the window that carries (3 f + 1.5) u."""
+    x = _bf16(torch.randn(64, 32, 8, 20, generator=torch.Generator().manual_seed(0)))
+    assert bool((cb._bilinear_coordinate_noise(x, (16, 40)) == 0).all())
+    sy, sx = torch.tensor(8., dtype=torch.float32) / 17, torch.tensor(20., dtype=torch.float32) / 41
+    fy = ((torch.arange(17, dtype=torch.float32) + .5) * sy - .5).clamp_min(0.)
+    fx = ((torch.arange(41, dtype=torch.float32) + .5) * sx - .5).clamp_min(0.)
+    y0, x0 = fy.long(), fx.long()
+    y1, x1 = (y0 + 1).clamp_max(7), (x0 + 1).clamp_max(19)
+    ly, lx = (fy - y0)[:, None], fx - x0
+    a = lambda yy, xx: x[:, :, yy][:, :, :, xx]
+    kernel = _bf16((1 - ly) * ((1 - lx) * a(y0, x0) + lx * a(y0, x1)) + ly * ((1 - lx) * a(y1, x0) + lx * a(y1, x1))).double()
+    exact = F.interpolate(x.double(), size=(17, 41), mode='bilinear', align_corners=False)
+    s = F.interpolate(x.double().abs(), size=(17, 41), mode='bilinear', align_corners=False)
+    mid, half = cb.hidden_bf16(exact, cb.gamma(8) * s)
+    assert int(((kernel < mid - half) | (kernel > mid + half)).sum()) > 0
+    mid, half = cb.bilinear_bf16_operand(x, (17, 41))
+    assert int(((kernel < mid - half) | (kernel > mid + half)).sum()) == 0
+    # (3 f + 1.5) u < 2^-18 at f < 20, adjacent pixels differ by at most 2 max|x|, two axes: far below a bf16 ulp (2^-8)
+    assert float(cb._bilinear_coordinate_noise(x, (17, 41)).max()) <= 2. ** -16 * float(x.abs().max())
 
 
 # ---- mutants are rejected, on every seed ---------------------------------------------------------------------------

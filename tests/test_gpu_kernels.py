@@ -49,6 +49,39 @@ def from_nhwc(y, c):
 guarded, assert_guards, BF16_GUARD, F32_GUARD = cb.guarded, cb.assert_guards, cb.BF16_GUARD, cb.F32_GUARD
 
 
+def conv_plan(*, cin, cout, k, stride=1, groups=1, bias=True, bn=True, act='relu', cin1=0, up0=False, up1=False, res=False,
+              res_up=False, out_f32=False, act_scale=3., seed=0, fuse_cout=0, fuse_act='none', bilinear=False, **_):
+    """The one-conv plan of run_conv and its seeded parameters -> (plan, state dict, generator); needs no GPU
+    (tests/conv_tiles.py asks the library which kernel the same plan runs)."""
+    from celldetection_amd import _lib, graph
+    g = torch.Generator().manual_seed(seed)
+    P = graph.Plan()
+    s0 = P.tensor(cin, 2 if (up0 or bilinear) else 1)
+    if bilinear:  # source stored at half resolution, read through the fused bilinear resize (MODE_BL)
+        up0 = 'bilinear'
+    s1 = P.tensor(cin1, 2 if up1 else 1) if cin1 else None
+    r = P.tensor(cout, (2 if res_up else 1) * stride) if res else None
+    P.conv(s0, cout, k, w='c.', bn='b.' if bn else None, bias=bias, stride=stride, groups=groups, act=act,
+           act_scale=act_scale, src1=s1, up0=up0, up1=up1, res=r, res_up=res_up,
+           out_index=_lib.OUT_SCORES if (out_f32 or fuse_cout) else None,
+           fuse=dict(w='f.', cout=fuse_cout, act=fuse_act, act_scale=act_scale) if fuse_cout else None)
+    return P, random_state_dict(P, g), g
+
+
+def random_state_dict(P, g):
+    sd = {}
+    for key, shape, kind in P.entries:
+        if key.endswith('running_var'):
+            sd[key] = torch.rand(shape, generator=g) + .5
+        elif key.endswith('num_batches_tracked'):
+            sd[key] = torch.zeros((), dtype=torch.long)
+        elif len(shape) == 4:
+            sd[key] = torch.randn(shape, generator=g) / np.sqrt(np.prod(shape[1:]))
+        else:
+            sd[key] = torch.randn(shape, generator=g) * .5 + (1. if key.endswith('b.weight') else 0.)
+    return sd
+
+
 def run_conv(dev, *, n, h, w, cin, cout, k, stride=1, groups=1, bias=True, bn=True, act='relu', cin1=0, up0=False,
              up1=False, res=False, res_up=False, out_f32=False, act_scale=3., seed=0, fuse_cout=0, fuse_act='none',
              bilinear=False, reference=True):
@@ -61,29 +94,12 @@ def run_conv(dev, *, n, h, w, cin, cout, k, stride=1, groups=1, bias=True, bn=Tr
     Resized sources are stored at (Hin >> 1, Win >> 1) and read through the nearest rule floor(dst * Hs / Hin) of
     F.interpolate(size=...): odd Hin / Win included."""
     from celldetection_amd import _lib, graph
-    g = torch.Generator().manual_seed(seed)
-    P = graph.Plan()
+    P, sd, g = conv_plan(cin=cin, cout=cout, k=k, stride=stride, groups=groups, bias=bias, bn=bn, act=act, cin1=cin1, up0=up0,
+                         up1=up1, res=res, res_up=res_up, out_f32=out_f32, act_scale=act_scale, seed=seed, fuse_cout=fuse_cout,
+                         fuse_act=fuse_act, bilinear=bilinear)
     hin, win = h, w
-    s0 = P.tensor(cin, 2 if (up0 or bilinear) else 1)
-    if bilinear:  # source stored at half resolution, read through the fused bilinear resize (MODE_BL)
-        up0 = 'bilinear'
-    s1 = P.tensor(cin1, 2 if up1 else 1) if cin1 else None
-    r = P.tensor(cout, (2 if res_up else 1) * stride) if res else None
-    P.conv(s0, cout, k, w='c.', bn='b.' if bn else None, bias=bias, stride=stride, groups=groups, act=act,
-           act_scale=act_scale, src1=s1, up0=up0, up1=up1, res=r, res_up=res_up,
-           out_index=_lib.OUT_SCORES if (out_f32 or fuse_cout) else None,
-           fuse=dict(w='f.', cout=fuse_cout, act=fuse_act, act_scale=act_scale) if fuse_cout else None)
+    up0 = up0 or bilinear
     out_f32 = out_f32 or bool(fuse_cout)
-    sd = {}
-    for key, shape, kind in P.entries:
-        if key.endswith('running_var'):
-            sd[key] = torch.rand(shape, generator=g) + .5
-        elif key.endswith('num_batches_tracked'):
-            sd[key] = torch.zeros((), dtype=torch.long)
-        elif len(shape) == 4:
-            sd[key] = torch.randn(shape, generator=g) / np.sqrt(np.prod(shape[1:]))
-        else:
-            sd[key] = torch.randn(shape, generator=g) * .5 + (1. if key.endswith('b.weight') else 0.)
     tens, ops, wblob, bblob = graph.pack(P, sd, dev)
     op = ops[0]
 
@@ -155,7 +171,7 @@ CONV_CASES = {
     '1x1_s2': dict(n=2, h=32, w=32, cin=64, cout=128, k=1, stride=2, act='none'),
     '3x3_64_64': dict(n=2, h=32, w=32, cin=64, cout=64, k=3),
     '3x3_odd_channels': dict(n=1, h=32, w=64, cin=8, cout=24, k=3),
-    '3x3_256_big_tile': dict(n=1, h=64, w=64, cin=64, cout=256, k=3),
+    '3x3_256_small_grid_4x64_tile': dict(n=1, h=64, w=64, cin=64, cout=256, k=3),  # 128 blocks at 4x256: the grid shrinks the tile
     '3x3_s2': dict(n=2, h=64, w=64, cin=32, cout=64, k=3, stride=2),
     '3x3_grouped_cpg8': dict(n=1, h=32, w=32, cin=256, cout=256, k=3, groups=32),
     '3x3_grouped_cpg64_s2': dict(n=1, h=32, w=32, cin=128, cout=128, k=3, groups=2, stride=2),
@@ -174,7 +190,8 @@ CONV_CASES = {
     'c64_fused_head_th16': dict(n=4, h=256, w=256, cin=64, cout=64, k=7, fuse_cout=2, fuse_act='tanh_scaled', seed=11),
     'c64_concat_up_partial': dict(n=3, h=40, w=72, cin=32, cout=64, k=3, cin1=64, up1=True, seed=12),
     'c64_k5_three_chunks': dict(n=2, h=64, w=64, cin=96, cout=64, k=5, seed=13),
-    # sizes at which the flagship 8x256 tile is what launch_conv selects
+    # 1024 blocks of 8 x 32 x 128: the plain 3x3 runs MODE_S1F <8,128,4,2>; the concat source and the fused head keep the flagship
+    # <8,256,4,2> tile (tests/conv_tiles.py RECORDED holds what every case here runs; tests/test_conv_tiles.py asserts it)
     '3x3_256_flagship_tile': dict(n=8, h=128, w=128, cin=64, cout=256, k=3),
     '3x3_256_flagship_concat_up': dict(n=8, h=128, w=128, cin=32, cout=256, k=3, cin1=64, up1=True, seed=7),
     'fused_head_256_flagship_tile': dict(n=8, h=128, w=128, cin=96, cout=256, k=7, fuse_cout=20, fuse_act='none', seed=9),
@@ -247,7 +264,9 @@ def test_conv_two_workgroups_per_cu_mode(dev, name, monkeypatch):
 
 
 S1Q_CASES = {
-    # MODE_S1Q (four K items per pipeline step, flat pitch-40 halo tiles) on the 64-output-channel 5x5 / 7x7 convs
+    # MODE_S1Q (four K items per pipeline step, flat pitch-40 halo tiles) on the 64-output-channel 5x5 / 7x7 convs.  The mode needs
+    # 448 tiles of 16 x 32: the first two cases run it, the last three (320, 288 and 256 tiles) run MODE_S1 <8,64,2,2> under either
+    # switch value (tests/conv_tiles.py RECORDED); bf16/S1Q/16x64 and its +res entry there are the ragged / residual cases of the mode
     's1q_7x7_64_64': dict(n=4, h=256, w=256, cin=64, cout=64, k=7, seed=41),                      # 98 items -> 100 (two read zeros)
     's1q_7x7_fused_head': dict(n=4, h=256, w=256, cin=64, cout=64, k=7, fuse_cout=2, fuse_act='tanh_scaled', seed=42),
     's1q_7x7_one_chunk': dict(n=8, h=128, w=160, cin=32, cout=64, k=7, seed=43),                   # 49 items -> 52 (three read zeros)
@@ -282,6 +301,22 @@ SUBPIXEL_CASES = {
 }
 
 
+def subpixel_plan(c):
+    """The three-op plan (HEAD, PHASE, LATERAL) of test_subpixel_decoder_conv and its seeded parameters -> (plan, state dict,
+    generator, id of the partial-sum tensor); needs no GPU."""
+    from celldetection_amd import graph
+    c = dict(dict(bias=True, seed=0), **c)
+    c0, c1, cout = (c[k] for k in ('c0', 'c1', 'cout'))
+    g = torch.Generator().manual_seed(c['seed'])
+    P = graph.Plan()
+    lat, top = P.tensor(c0, 1), P.tensor(c1, 2)
+    kw = dict(w='c.', bn='b.', bias=c['bias'])
+    x = P.conv(lat, cout, 3, act='relu', src1=top, up1=True, sub='head', **kw)
+    ph = P.conv(top, cout, 2, pad=1, sub=('phase', c0), **kw)
+    P.conv(lat, cout, 3, act='relu', res=ph, res_up='shuffle', sub=('lateral', c0), dst=x, **kw)
+    return P, random_state_dict(P, g), g, ph
+
+
 @pytest.mark.parametrize('name', list(SUBPIXEL_CASES))
 def test_subpixel_decoder_conv(dev, name):
     """Sub-pixel triple of a UNet decoder conv over cat(lateral, nearest-x2-upsampled top-down map)
@@ -294,23 +329,7 @@ def test_subpixel_decoder_conv(dev, name):
     c = dict(bias=True, seed=0)
     c.update(SUBPIXEL_CASES[name])
     n, h, w, c0, c1, cout = (c[k] for k in ('n', 'h', 'w', 'c0', 'c1', 'cout'))
-    g = torch.Generator().manual_seed(c['seed'])
-    P = graph.Plan()
-    lat, top = P.tensor(c0, 1), P.tensor(c1, 2)
-    kw = dict(w='c.', bn='b.', bias=c['bias'])
-    x = P.conv(lat, cout, 3, act='relu', src1=top, up1=True, sub='head', **kw)
-    ph = P.conv(top, cout, 2, pad=1, sub=('phase', c0), **kw)
-    P.conv(lat, cout, 3, act='relu', res=ph, res_up='shuffle', sub=('lateral', c0), dst=x, **kw)
-    sd = {}
-    for key, shape, kind in P.entries:
-        if key.endswith('running_var'):
-            sd[key] = torch.rand(shape, generator=g) + .5
-        elif key.endswith('num_batches_tracked'):
-            sd[key] = torch.zeros((), dtype=torch.long)
-        elif len(shape) == 4:
-            sd[key] = torch.randn(shape, generator=g) / np.sqrt(np.prod(shape[1:]))
-        else:
-            sd[key] = torch.randn(shape, generator=g) * .5 + (1. if key.endswith('b.weight') else 0.)
+    P, sd, g, ph = subpixel_plan(c)
     tens, ops, wblob, bblob = graph.pack(P, sd, dev)
     assert [o.subpixel for o in ops] == [_lib.SUBPIXEL_HEAD, _lib.SUBPIXEL_PHASE, _lib.SUBPIXEL_LATERAL]
     assert tens[ph].channels == 4 * _pad32(cout)
@@ -709,7 +728,7 @@ FP8_CASES = {
     '1x1_odd_chunks_res': dict(n=1, h=32, w=64, cin=192, cout=128, k=1, res=True),
     '3x3_odd_channels': dict(n=1, h=32, w=64, cin=24, cout=40, k=3),
     '3x3_s2': dict(n=2, h=64, w=64, cin=64, cout=128, k=3, stride=2),
-    '7x7_256_big_tile': dict(n=1, h=64, w=64, cin=128, cout=256, k=7),
+    '7x7_256_small_grid_4x64_tile': dict(n=1, h=64, w=64, cin=128, cout=256, k=7),  # 128 blocks at 4x256: the grid shrinks the tile
     '3x3_concat_up': dict(n=2, h=32, w=32, cin=64, cout=64, k=3, cin1=128, up1=True),
     '3x3_grouped_cpg8': dict(n=1, h=32, w=32, cin=256, cout=256, k=3, groups=32),
     '7x7_stem_s2': dict(n=2, h=64, w=64, cin=3, cout=64, k=7, stride=2, bias=False),
@@ -719,20 +738,15 @@ FP8_CASES = {
 }
 
 
-@pytest.mark.parametrize('name', list(FP8_CASES))
-def test_conv_fp8_vs_dequantised_reference(dev, name):
-    """fp8 conv kernel vs the fp64 conv of the SAME e4m3 operands (input codes x their scale, the packer's weight codes x
-    their per-channel scale: graph.pack(effective_weights=...)): every output within the rounding bound of
-    tests/conv_bounds.py -- e4m3 outputs one of the codes RNE can produce from the accumulation-noise window, at the
-    output's code scale; fp32 outputs within the noise + 4 ulp.  No allowance.  Guard rows around the output come back
-    untouched, and every padded output code is a zero (0x00 or 0x80)."""
+def conv_fp8_plan(cfg):
+    """The one-conv plan of run_conv_fp8 and its seeded parameters -> (plan, state dict, generator, (s0, s1, r) tensor ids);
+    needs no GPU."""
     from celldetection_amd import _lib, graph
-    cfg = dict(FP8_CASES[name])
-    n, h, w, cin, cout, k = (cfg[x] for x in ('n', 'h', 'w', 'cin', 'cout', 'k'))
+    cin, cout, k = (cfg[x] for x in ('cin', 'cout', 'k'))
     stride, groups, cin1, up1 = cfg.get('stride', 1), cfg.get('groups', 1), cfg.get('cin1', 0), cfg.get('up1', False)
     res, act, out_f32, fuse_cout = cfg.get('res', False), cfg.get('act', 'relu'), cfg.get('out_f32', False), \
         cfg.get('fuse_cout', 0)
-    g = torch.Generator().manual_seed(11)
+    g = torch.Generator().manual_seed(cfg.get('seed', 11))
     P = graph.Plan()
     s0 = P.tensor(cin, 1)
     s1 = P.tensor(cin1, 2 if up1 else 1) if cin1 else None
@@ -741,17 +755,23 @@ def test_conv_fp8_vs_dequantised_reference(dev, name):
            groups=groups, act=act, src1=s1, up1=up1, res=r,
            out_index=_lib.OUT_SCORES if (out_f32 or fuse_cout) else None,
            fuse=dict(w='f.', cout=fuse_cout, act=cfg.get('fuse_act', 'none'), act_scale=3.) if fuse_cout else None)
+    return P, random_state_dict(P, g), g, (s0, s1, r)
+
+
+def run_conv_fp8(dev, name, **cfg):
+    """fp8 conv kernel vs the fp64 conv of the SAME e4m3 operands (input codes x their scale, the packer's weight codes x
+    their per-channel scale: graph.pack(effective_weights=...)): every output within the rounding bound of
+    tests/conv_bounds.py -- e4m3 outputs one of the codes RNE can produce from the accumulation-noise window, at the
+    output's code scale; fp32 outputs within the noise + 4 ulp.  No allowance.  Guard rows around the output come back
+    untouched, and every padded output code is a zero (0x00 or 0x80).  -> max |got - ref| / bound; a BoundError carries
+    .got / .lo / .hi / .ref (NCHW) for the caller's report."""
+    from celldetection_amd import _lib, graph
+    n, h, w, cin, cout, k = (cfg[x] for x in ('n', 'h', 'w', 'cin', 'cout', 'k'))
+    stride, groups, cin1, up1 = cfg.get('stride', 1), cfg.get('groups', 1), cfg.get('cin1', 0), cfg.get('up1', False)
+    res, act, out_f32, fuse_cout = cfg.get('res', False), cfg.get('act', 'relu'), cfg.get('out_f32', False), \
+        cfg.get('fuse_cout', 0)
+    P, sd, g, (s0, s1, r) = conv_fp8_plan(cfg)
     out_f32 = out_f32 or bool(fuse_cout)
-    sd = {}
-    for key, shape, kind in P.entries:
-        if key.endswith('running_var'):
-            sd[key] = torch.rand(shape, generator=g) + .5
-        elif key.endswith('num_batches_tracked'):
-            sd[key] = torch.zeros((), dtype=torch.long)
-        elif len(shape) == 4:
-            sd[key] = torch.randn(shape, generator=g) / np.sqrt(np.prod(shape[1:]))
-        else:
-            sd[key] = torch.randn(shape, generator=g) * .5 + (1. if key.endswith('b.weight') else 0.)
     x0 = torch.randn(n, cin, h, w, generator=g)
     x1 = torch.randn(n, cin1, h // 2 if up1 else h, w // 2 if up1 else w, generator=g) * 2 if cin1 else None
     ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (w + 2 * (k // 2) - k) // stride + 1
@@ -834,7 +854,7 @@ def test_conv_fp8_vs_dequantised_reference(dev, name):
             FP8_BLOCK_ERR.append(blk)
             print(f'{name}: e4m3 block sum error max |got - ref| / S = {blk:.3e} = 2^{math.log2(max(blk, 1e-300)):.2f}')
         lo, hi = cb.f32_bounds(ref, d, act, 3.)
-        ratio = cb.check(name, dst.cpu(), lo, hi, cb.apply_act(ref, act, 3.), S)
+        got, ref = dst.cpu(), cb.apply_act(ref, act, 3.)
     else:
         codes = dst.cpu()
         pad = codes[..., cout:]
@@ -843,8 +863,21 @@ def test_conv_fp8_vs_dequantised_reference(dev, name):
         got = codes[..., :cout].permute(0, 3, 1, 2).contiguous().view(torch.float8_e4m3fn).double()
         inv = f32_(op_scales[0][1])
         lo, hi = cb.e4m3_bounds(ref, d, inv, act)
-        ratio = cb.check(name, got, lo, hi, cb.apply_act(ref, act) * inv, S)
+        ref = cb.apply_act(ref, act) * inv
+    try:
+        ratio = cb.check(name, got, lo, hi, ref, S)
+    except cb.BoundError as e:
+        e.got, e.lo, e.hi, e.ref = got, lo, hi, ref
+        raise
     print(f'{name}: max |got - ref| / bound = {ratio:.3g}')
+    return ratio
+
+
+@pytest.mark.parametrize('name', list(FP8_CASES))
+def test_conv_fp8_vs_dequantised_reference(dev, name):
+    """Every FP8_CASES shape through run_conv_fp8: the e4m3 kernel within the rounding bound of the fp64 conv of the same e4m3
+    operands (tests/test_gpu_conv_tiles.py runs the same check once per kernel instantiation)."""
+    run_conv_fp8(dev, name, **FP8_CASES[name])
 
 
 @pytest.mark.parametrize('nb', [6, 3])
