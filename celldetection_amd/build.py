@@ -33,9 +33,13 @@ SOURCES = {
     'region_props.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
+    # the native graph executor (host code only; cpn_plan.h names the units)
+    'plan_validate.hip': [],
+    'plan_shapes.hip': [],
+    'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'lds_dma.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():
