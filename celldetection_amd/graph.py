@@ -1,9 +1,9 @@
-"""Layer plans of the CPN model families and weight packing for the HIP conv engine.
+"""Layer plans of the CPN model families for the HIP conv engine.
 
 A *plan* is built from constructor hyper-parameters only (no weights): an ordered list of state-dict entries
 (names + shapes identical to the reference's ``state_dict()``, so reference checkpoints load unchanged) and a small
-IR of fused ops (conv + folded BN + activation (+ residual / virtual concat / nearest upsample)).  ``pack`` turns a
-state dict into the bf16 weight blob + fp32 bias blob + ``cpn_op_desc`` array the native executor consumes.
+IR of fused ops (conv + folded BN + activation (+ residual / virtual concat / nearest upsample)).  ``pack.pack`` (re-exported
+here) turns a plan + a state dict into the weight blob, the bias blob and the ``cpn_op_desc`` array the native executor consumes.
 
 Reference structures mirrored (file:line relative to the reference repository):
   ResNet / ResNeXt encoders   celldetection/models/resnet.py:56-193,265-297,300-460
@@ -15,15 +15,21 @@ Reference structures mirrored (file:line relative to the reference repository):
 import math
 import os
 
-import torch
-
 from . import _lib
+from .pack import _ACT, _bundle_geometry, _fold, _pad32, _sub_kind, pack  # noqa: F401  (pack, _fold: re-exported)
 
 __all__ = ['Plan', 'build_plan', 'BACKBONES']
 
+_MEMBERS = ('phase', 'lateral', 'blphase', 'blframe')  # ``sub`` kinds of ops that restate (a part of) the head op in front of them
 
-def _pad32(c):
-    return (int(c) + 31) // 32 * 32
+
+def _input_down(down, up0, scatter=False):
+    """Down factor at which a conv op reads its first source (tensor at factor ``down``): 1 through the bilinear resize to the
+    input size, half of it through the nearest x2 upsample -- which a scatter conv stands for, too."""
+    if up0 == 'bilinear':
+        return 1
+    assert down % (2 if (up0 or scatter) else 1) == 0
+    return down // (2 if (up0 or scatter) else 1)
 
 
 class Plan:
@@ -44,6 +50,13 @@ class Plan:
                          (prefix + 'running_mean', (c,), 'buffer'), (prefix + 'running_var', (c,), 'buffer'),
                          (prefix + 'num_batches_tracked', (), 'long')]
 
+    def cut_entries(self, mark):
+        """Removes and returns the entries added since ``mark`` = len(entries) then: ops are built in execution order, their
+        state-dict entries are registered later, in the reference's order."""
+        cut = self.entries[mark:]
+        del self.entries[mark:]
+        return cut
+
     # ---- IR
     def tensor(self, c, down, phases=1):
         """``phases`` = 4: sub-pixel phase tensor, channel layout [phase (py, px)][padded c] (see ``conv(sub='phase')``)."""
@@ -61,26 +74,20 @@ class Plan:
         entries the caller registers itself (``_head_input``: Fuse2d over three and more features as partial 1x1 convs); a
         fourth element c = the first source is the running sum of the parts so far (c channels, identity weights)."""
         pad = k // 2 if pad is None else pad
-        t0 = self.tensors[src0]
-        if up0 == 'bilinear':  # source read through a bilinear resize to the input size (nominal down factor 1)
-            assert src1 is None and stride == 1 and k > 1
-            down_in = 1
-        else:
-            down_in = t0['down'] // (2 if up0 else 1)
-            assert t0['down'] % (2 if up0 else 1) == 0
+        t0, kind = self.tensors[src0], _sub_kind(sub)
+        scatter = kind == 'scatter'  # stands for a 3x3 conv over the x2-upsampled source
+        assert up0 != 'bilinear' or (src1 is None and stride == 1 and k > 1)
+        assert not scatter or (src1 is None and not up0 and k == 2)
+        down_in = _input_down(t0['down'], up0, scatter)
         cin = t0['c'] + (self.tensors[src1]['c'] if src1 is not None else 0)
         if src1 is not None and not up1:  # (a resized second source takes the size of the first one: any ratio)
             assert self.tensors[src1]['down'] == down_in
         down_out = down_in * stride
-        scatter = isinstance(sub, tuple) and sub[0] == 'scatter'  # stands for a 3x3 conv over the x2-upsampled source
-        if isinstance(sub, tuple) and sub[0] == 'blphase':  # bilinear phases: low-resolution source, full-resolution output
+        if kind == 'blphase':  # bilinear phases: low-resolution source, full-resolution output
             down_out = max(t0['down'] // 2, 1)
-        if scatter:
-            assert t0['down'] % 2 == 0 and src1 is None and not up0 and k == 2
-            down_out = t0['down'] // 2
-        member = (isinstance(sub, tuple) and not scatter) or share is not None  # no state-dict entries of its own
+        member = kind in _MEMBERS or share is not None  # no state-dict entries of its own
         if dst is None:
-            dst = self.tensor(cout, down_out, phases=4 if (isinstance(sub, tuple) and sub[0] == 'phase') else 1) if out_index is None else None
+            dst = self.tensor(cout, down_out, phases=4 if kind == 'phase' else 1) if out_index is None else None
         if not member:
             self.conv_keys(w, cout, cin // groups, 3 if scatter else k, bias)
             if bn is not None:
@@ -99,8 +106,8 @@ class Plan:
         csrc/conv_pair.hip).  The executor runs it instead of the pair wherever the kernel's tiles fit and fill the chip;
         no state-dict entries, no weights of its own.  Returns False (and adds nothing) when the pair does not qualify."""
         c1, c2 = self.ops[-2], self.ops[-1]
-        cpg = c2['cin'] // c2['groups']
-        bw = cpg if cpg % 32 == 0 else (32 if 32 % cpg == 0 else 0)  # channels per packed bundle (_bundle_geometry)
+        geo = _bundle_geometry(c2['cin'], c2['cout'], c2['groups'])
+        bw = geo[1] if geo else 0  # channels per packed bundle
         ok = (c1['op'] == c2['op'] == 'conv' and c1['k'] == 1 and c1['stride'] == 1 and c1['groups'] == 1 and
               c1['src1'] is None and c1['res'] is None and not c1['up0'] and c1['act'] == 'relu' and c1.get('sub') is None and
               c2['src0'] == c1['dst'] and c2['k'] == 3 and c2['stride'] in (1, 2) and c2['pad'] == 1 and c2['groups'] > 1 and
@@ -118,11 +125,10 @@ class Plan:
         them stays in LDS.  The executor runs it instead of the pair wherever the output holds a 16 x 32 tile; no state-dict
         entries, no weights of its own.  Returns False (and adds nothing) when the pair does not qualify."""
         c1, c2 = self.ops[-2], self.ops[-1]
-        p32 = lambda c: (c + 31) // 32 * 32
-        ok = (c1['op'] == c2['op'] == 'conv' and isinstance(c1.get('sub'), tuple) and c1['sub'][0] == 'scatter' and
-              c1['act'] == 'relu' and p32(c1['cout']) == 64 and p32(c1['cin']) in (32, 64) and c1['dst'] is not None and
+        ok = (c1['op'] == c2['op'] == 'conv' and _sub_kind(c1.get('sub')) == 'scatter' and
+              c1['act'] == 'relu' and _pad32(c1['cout']) == 64 and _pad32(c1['cin']) in (32, 64) and c1['dst'] is not None and
               c2['src0'] == c1['dst'] and c2['src1'] is None and not c2['up0'] and c2['k'] == 3 and c2['stride'] == 1 and
-              c2['pad'] == 1 and c2['groups'] == 1 and p32(c2['cout']) == 64 and c2.get('sub') is None and c2['dst'] is not None and
+              c2['pad'] == 1 and c2['groups'] == 1 and _pad32(c2['cout']) == 64 and c2.get('sub') is None and c2['dst'] is not None and
               c2['fuse'] is None and c2['res_up'] in (False, 0, 'shuffle'))
         if ok:
             self.ops.append(dict(op='conv_bridge', src0=c1['src0'], dst=c2['dst'], res=c2['res'], first=len(self.ops) - 2,
@@ -170,7 +176,7 @@ class Plan:
         while moved:
             moved = False
             while ready < begin and (self.ops[ready].get('op') in ('conv_pair', 'conv_bridge') or self.ops[ready].get('alt') == 2 or
-                                     (isinstance(self.ops[ready].get('sub'), tuple) and self.ops[ready]['sub'][0] != 'scatter')):
+                                     _sub_kind(self.ops[ready].get('sub')) in _MEMBERS):
                 ready += 1  # (a scatter conv OPENS a unit -- the block may go in front of it)
             # a fused op + the two convs it restates ([first, first + 1, fused]) are one unit: never insert inside it (the
             # ResNet18/34-UNets have no inner_blocks.0, so their bridge's scatter conv directly follows the heads' producer)
@@ -333,30 +339,17 @@ def _resnet(P, x, in_channels, prefix, kind, base_channel=64, stem_fast=False, f
                 t = P.conv(t, width, 3, w=p + 'conv2.', bn=p + 'bn2.', stride=stride, groups=groups, act='relu')
                 if fuse_blocks and groups > 1:
                     P.conv_pair()  # (bf16 plans) conv1 -> grouped conv2 as one kernel where the feature map allows it
-                # key order in the reference: conv3, bn3, then downsample -> emit conv3 keys before downsample keys
-                n_before = len(P.entries)
-                out_c = planes * expansion
-                if has_ds:
-                    # IR order: downsample must exist before conv3 (residual); entries order fixed afterwards
-                    idt = P.conv(x, out_c, 1, w=p + 'downsample.0.', bn=p + 'downsample.1.', stride=stride)
-                    ds_entries = P.entries[n_before:]
-                    del P.entries[n_before:]
-                else:
-                    idt, ds_entries = x, []
+            # IR order: downsample must exist before the conv that adds it (residual); key order in the reference: the block's
+            # convs and norms, then downsample -> its entries are registered behind them
+            out_c, mark = planes * expansion, len(P.entries)
+            idt = P.conv(x, out_c, 1, w=p + 'downsample.0.', bn=p + 'downsample.1.', stride=stride) if has_ds else x
+            ds_entries = P.cut_entries(mark)
+            if block == 'bottle':
                 x = P.conv(t, out_c, 1, w=p + 'conv3.', bn=p + 'bn3.', res=idt, act='relu')
-                P.entries += ds_entries
             else:
-                out_c = planes
-                n_before = len(P.entries)
-                if has_ds:
-                    idt = P.conv(x, out_c, 1, w=p + 'downsample.0.', bn=p + 'downsample.1.', stride=stride)
-                    ds_entries = P.entries[n_before:]
-                    del P.entries[n_before:]
-                else:
-                    idt, ds_entries = x, []
                 t = P.conv(x, planes, 3, w=p + 'conv1.', bn=p + 'bn1.', stride=stride, act='relu')
                 x = P.conv(t, planes, 3, w=p + 'conv2.', bn=p + 'bn2.', res=idt, act='relu')
-                P.entries += ds_entries
+            P.entries += ds_entries
             inplanes = planes * expansion
         feats.append(x)
         channels.append(inplanes)
@@ -387,15 +380,14 @@ def _generalized_unet(P, feats, channels, strides, prefix, subpixel=False, res_b
     depth = n - 1
     last = feats[-1]
     results = {}
-    entries_inner, entries_layer = {}, {}
+    entries_inner, entries_layer = [], []  # levels are built top-down and registered bottom-up
     for i in range(depth - 1, -1, -1):
         lat = feats[i - bridges] if (i - bridges) >= 0 else None
         top = last
         mark = len(P.entries)
         if inner[i] is not None:
             top = P.conv(top, inner[i][1], 1, w=f'{prefix}inner_blocks.{i}.', bias=True)
-        entries_inner[i] = P.entries[mark:]
-        del P.entries[mark:]
+        entries_inner[:0] = P.cut_entries(mark)
         ouc = out_list[i]
         if lat is not None and res_blocks:
             last = _cd_res_block(P, lat, P.tensors[lat]['c'] + P.tensors[top]['c'], ouc, f'{prefix}layer_blocks.{i}.', src1=top,
@@ -405,15 +397,11 @@ def _generalized_unet(P, feats, channels, strides, prefix, subpixel=False, res_b
                                        subpixel=subpixel)
         else:
             last = _two_conv_norm_relu(P, top, ouc, f'{prefix}layer_blocks.{i}.', bias=False, up0=True, subpixel=subpixel)
-        entries_layer[i] = P.entries[mark:]
-        del P.entries[mark:]
+        entries_layer[:0] = P.cut_entries(mark)
         results[i] = last
     results[depth] = feats[-1]  # the dict of the reference ends with the deepest encoder feature itself (unet.py:207-249)
     out_list = list(out_list) + [channels[-1]] if len(out_list) <= depth else list(out_list)
-    for i in sorted(entries_inner):
-        P.entries += entries_inner[i]
-    for i in sorted(entries_layer):
-        P.entries += entries_layer[i]
+    P.entries += entries_inner + entries_layer
     return results, out_list
 
 
@@ -422,25 +410,20 @@ def _fpn(P, feats, channels, prefix, fpn_channels, live=(0, 1)):
     top-down nearest upsample + add (fused as an upsampled residual), 3x3 output convs.  Levels whose outputs the CPN
     never reads (layer_blocks 2..4, 'pool') are skipped but their parameters stay in the state dict."""
     n = len(feats)
-    lat_entries, out_entries = {}, {}
+    lat_entries, out_entries = [], []  # levels are built top-down and registered bottom-up
     last = None
     outs = {}
     for idx in range(n - 1, -1, -1):
         mark = len(P.entries)
         last = P.conv(feats[idx], fpn_channels, 1, w=f'{prefix}inner_blocks.{idx}.0.', bias=True,
                       res=last, res_up=last is not None)
-        lat_entries[idx] = P.entries[mark:]
-        del P.entries[mark:]
+        lat_entries[:0] = P.cut_entries(mark)
         if idx in live:
             outs[idx] = P.conv(last, fpn_channels, 3, w=f'{prefix}layer_blocks.{idx}.0.', bias=True)
         else:  # dead level: keep the parameters only
             P.conv_keys(f'{prefix}layer_blocks.{idx}.0.', fpn_channels, fpn_channels, 3, True)
-        out_entries[idx] = P.entries[mark:]
-        del P.entries[mark:]
-    for idx in range(n):
-        P.entries += lat_entries[idx]
-    for idx in range(n):
-        P.entries += out_entries[idx]
+        out_entries[:0] = P.cut_entries(mark)
+    P.entries += lat_entries + out_entries
     return outs
 
 
@@ -728,12 +711,6 @@ def build_plan(backbone: str, in_channels: int, order: int = 5, score_channels: 
     return P
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# packing
-# ---------------------------------------------------------------------------------------------------------------------
-_ACT = {'none': _lib.ACT_NONE, 'relu': _lib.ACT_RELU, 'sigmoid': _lib.ACT_SIGMOID, 'tanh_scaled': _lib.ACT_TANH_SCALED,
-        'leaky_relu': _lib.ACT_LEAKY_RELU, 'silu': _lib.ACT_SILU, 'gelu': _lib.ACT_GELU, 'elu': _lib.ACT_ELU, 'tanh': _lib.ACT_TANH,
-        'hardswish': _lib.ACT_HARDSWISH, 'mish': _lib.ACT_MISH, 'selu': _lib.ACT_SELU, 'softplus': _lib.ACT_SOFTPLUS}
 # hidden activations of the ReadOut heads (``head_activation*`` of models/cpn.py:183-233 -> ``lookup_nn(name)``: the torch.nn module
 # of that name, case-insensitive, default arguments) -> activation names of the plan
 HEAD_ACTIVATIONS = {'relu': 'relu', 'leakyrelu': 'leaky_relu', 'silu': 'silu', 'gelu': 'gelu', 'elu': 'elu', 'tanh': 'tanh',
@@ -751,341 +728,18 @@ def head_activation_name(value) -> str:
     return HEAD_ACTIVATIONS[key]
 
 
-def _fold(sd, op):
-    """Conv weight/bias with eval-mode BatchNorm (eps 1e-5) folded in, float64 math."""
-    w = sd[op['w'] + 'weight'].detach().double().cpu()
-    cout = w.shape[0]
-    b = sd[op['w'] + 'bias'].detach().double().cpu() if op['bias'] else torch.zeros(cout, dtype=torch.float64)
-    if op['bn'] is not None:
-        g = sd[op['bn'] + 'weight'].detach().double().cpu()
-        beta = sd[op['bn'] + 'bias'].detach().double().cpu()
-        mu = sd[op['bn'] + 'running_mean'].detach().double().cpu()
-        var = sd[op['bn'] + 'running_var'].detach().double().cpu()
-        s = g / torch.sqrt(var + 1e-5)
-        w = w * s[:, None, None, None]
-        b = (b - mu) * s + beta
-    return w, b
-
-
-def _bundle_geometry(cin, cout, groups, kc=32):
-    """(bundles, cin_b, cout_b, groups_per_bundle) or None when the grouped conv must be densified
-    (kc = channels per weight record: 32 bf16 | 64 fp8)."""
-    if groups == 1:
-        return None
-    cig, cog = cin // groups, cout // groups
-    if cig != cog:
-        return None
-    bw = cig if cig % kc == 0 else (kc if kc % cig == 0 else None)
-    if bw is None or cin % bw:
-        return None
-    return cin // bw, bw, bw, bw // cig
-
-
-def _pad64(c):
-    return (c + 63) // 64 * 64
-
-
-def pack(plan: Plan, state_dict, device, precision: str = 'bf16', act_scales=None, effective_weights: list = None):
-    """-> (tensor_descs, op_descs, weight_blob[bf16 | f32, device], bias_blob[f32, device]).
-
-    bf16: weights [bundle][cin_b/32][k*k (+1 zero slab if the item count is odd)][cout_b][32]; fp32 (verification path): [bundle][k*k][cin_b][cout_b].
-    fp8 (e4m3, groundwork for BASELINE configs[4]): ``act_scales[tensor id]`` = value per activation code; channels
-    are padded to 64; weights [bundle][cin_b/64][k*k (+1 zero slab if odd)][cout_b][64] as e4m3 codes of
-    ``w * input_scale / weight_scale[cout]``; returns additionally (mult_blob[f32] = weight_scale per output channel,
-    [(res_scale, out_inv_scale)] per op); the weight blob is a byte tensor.  ``effective_weights`` (tests): a list that
-    receives, per conv op, the dequantised weights the fp8 kernel effectively applies to real-valued inputs
-    (``[cout, cin/groups, k, k]`` float64) and the bias."""
-    f32 = precision == 'fp32'
-    fp8 = precision == 'fp8'
-    if fp8 and act_scales is None:
-        raise ValueError('fp8 packing needs the per-tensor activation scales')
-    _pad = _pad64 if fp8 else _pad32
-    KC = 64 if fp8 else 32  # channels per weight record
-    wdt, wsz = (torch.float32, 4) if f32 else (torch.bfloat16, 2)
-    if fp8:
-        wsz = 1
-    mparts, op_scales = [], []
-    tens = (_lib.TensorDesc * len(plan.tensors))()
-    for i, t in enumerate(plan.tensors):
-        tens[i].channels, tens[i].down = _pad(t['c']) * t.get('phases', 1), t['down']
-        # fp8 plans: the partial-sum tensor of a sub-pixel triple ([phase][c], ``phases`` == 4) is stored as bf16 -- flagged by a
-        # negative scale (include/cpn_hip.h cpn_tensor_desc)
-        tens[i].scale = (-1. if t.get('phases', 1) == 4 else float(act_scales[i])) if fp8 else 0.
-    ops = (_lib.OpDesc * len(plan.ops))()
-    wparts, bparts = [], []
-    woff = boff = 0
-    for i, op in enumerate(plan.ops):
-        d = ops[i]
-        d.src0 = d.src1 = d.res = d.dst = -1
-        d.bias_offset = d.mult_offset = -1
-        op_scales.append((0., 0.))
-        d.alt = int(op.get('alt', 0))
-        if d.alt and f32:
-            raise ValueError('the stem fast path is a bf16 / fp8-plan feature')
-        if op['op'] in ('input', 'input_stem'):
-            d.op, d.dst, d.in_channels = (_lib.OP_INPUT if op['op'] == 'input' else _lib.OP_INPUT_STEM), op['dst'], op['in_channels']
-            continue
-        if op['op'] == 'stem7':
-            # weights [7][cout_b][32] bf16: filter row ky, output channel, (kx 0..7, c 0..3) -- the 7 taps of a filter row
-            # over a 4-channel NHWC input are 28 contiguous values; kx = 7 and c >= in_channels meet zeros
-            # (fp8 plans: the stem computes in bf16 on the bf16 input, too -- only its OUTPUT is e4m3 codes of the dst
-            # tensor's scale; no weight quantisation, the multiplier slots that keep bias / mult indices aligned are ones)
-            w, b = _fold(state_dict, op)
-            cout, cin = op['cout'], op['cin']
-            coutp = _pad(cout)
-            wk = torch.zeros(7, coutp, 8, 4, dtype=torch.float64)
-            wk[:, :cout, :7, :cin] = w.permute(2, 0, 3, 1)  # [cout, cin, ky, kx] -> [ky, cout, kx, cin]
-            bias = torch.zeros(coutp, dtype=torch.float64)
-            bias[:cout] = b
-            wq = wk.reshape(-1).to(torch.bfloat16)
-            wparts.append(wq.view(torch.uint8) if fp8 else wq)
-            bparts.append(bias.to(torch.float32))
-            if fp8:
-                mparts.append(torch.ones(coutp, dtype=torch.float32))
-                op_scales[-1] = (0., 1. / float(act_scales[op['dst']]))
-            d.op, d.src0, d.dst = _lib.OP_STEM7, op['src0'], op['dst']
-            d.kh = d.kw = 7
-            d.stride, d.pad, d.bundles, d.cin_b, d.cout_b = 2, 3, 1, 32, coutp
-            d.weight_offset, d.bias_offset = woff, boff
-            d.act, d.cout_real, d.out_index = _lib.ACT_RELU, cout, -1
-            d.fuse_weight_offset = d.fuse_bias_offset = -1
-            woff += wq.numel() * 2
-            boff += bparts[-1].numel()
-            continue
-        if op['op'] == 'conv_pair':  # shares the packed weights / biases of the two convs in front of it
-            if f32 or fp8:
-                raise ValueError('fused bottleneck heads are a bf16-plan feature')
-            c1, c2 = ops[op['first']], ops[op['first'] + 1]
-            assert op['first'] == i - 2 and c2.bundles * c2.cout_b == c1.cout_b and c2.cin_b == c2.cout_b
-            assert c1.dst == c2.src0 and op['w'].startswith(plan.ops[op['first']]['w']), 'conv_pair must directly follow its two convs'
-            d.op, d.src0, d.dst = _lib.OP_CONV_PAIR, op['src0'], op['dst']
-            d.kh = d.kw = 3
-            d.stride, d.pad = c2.stride, 1
-            d.bundles, d.cin_b, d.cout_b, d.c0_used = c2.bundles, c1.cin_b, c1.cout_b, c1.cin_b
-            d.weight_offset, d.bias_offset = c1.weight_offset, c1.bias_offset
-            d.fuse_weight_offset, d.fuse_bias_offset, d.fuse_cout = c2.weight_offset, c2.bias_offset, c2.cout_b
-            d.act, d.fuse_act, d.out_index, d.cout_real = _lib.ACT_RELU, _lib.ACT_RELU, -1, c2.cout_real
-            continue
-        if op['op'] == 'conv_bridge':  # shares the packed weights / biases of the scatter conv and the 3x3 conv in front of it
-            if f32 or fp8:
-                raise ValueError('the fused bridge level is a bf16-plan feature')
-            c1, c2 = ops[op['first']], ops[op['first'] + 1]
-            assert op['first'] == i - 2 and c1.cout_b == c2.cin_b == c2.cout_b == 64
-            assert c1.subpixel == _lib.SUBPIXEL_SCATTER and c1.dst == c2.src0 and \
-                op['w'].startswith(plan.ops[op['first']]['w']), 'conv_bridge must directly follow its scatter conv + 3x3 conv'
-            d.op, d.src0, d.dst, d.res = _lib.OP_CONV_BRIDGE, op['src0'], op['dst'], c2.res
-            d.kh = d.kw = 3
-            d.stride, d.pad, d.bundles, d.cin_b, d.cout_b, d.c0_used = 1, 1, 1, c1.cin_b, 64, c1.cin_b
-            d.res_up, d.act, d.act_scale, d.out_index, d.cout_real = c2.res_up, c2.act, c2.act_scale, -1, c2.cout_real
-            d.weight_offset, d.bias_offset = c1.weight_offset, c1.bias_offset
-            d.fuse_weight_offset, d.fuse_bias_offset, d.fuse_cout = c2.weight_offset, c2.bias_offset, 0
-            continue
-        if op['op'] == 'act':
-            d.op, d.src0, d.dst, d.act = _lib.OP_ACT, op['src0'], op['dst'], _ACT[op['act']]
-            continue
-        if op['op'] == 'maxpool':
-            d.op, d.src0, d.dst = _lib.OP_MAXPOOL, op['src0'], op['dst']
-            d.kh = d.kw = op['k']
-            d.stride, d.pad = op['stride'], op['pad']
-            continue
-        if op['op'] == 'bilinear':
-            d.op, d.src0, d.dst = _lib.OP_BILINEAR, op['src0'], op['dst']
-            d.act = 1 if op.get('mode') == 'bicubic' else 0  # (include/cpn_hip.h: a resize op's act selects the mode)
-            if d.act and fp8:
-                raise NotImplementedError("refinement_interpolation='bicubic' is a bf16 / fp32-plan feature (bicubic weights are "
-                                          'negative in places: the result leaves the e4m3 range of its source)')
-            # feeds a bilinear sub-pixel triple: only the frame's neighbourhood of the map is needed when the phase convs run
-            d.subpixel = _lib.SUBPIXEL_BL_FRAME if op.get('ring_for_bl') else _lib.SUBPIXEL_NONE
-            continue
-        # conv
-        w, b = _fold(state_dict, op)
-        k, groups, cin, cout = op['k'], op['groups'], op['cin'], op['cout']
-        sub = op.get('sub')
-        bl = sub == 'blhead' or (isinstance(sub, tuple) and sub[0] in ('blphase', 'blframe'))
-        if sub is not None and (f32 or (fp8 and isinstance(sub, tuple) and sub[0] == 'scatter')):
-            raise ValueError('sub-pixel conv triples are a bf16 / fp8-plan feature (the scattered bridge form: bf16)')
-        if isinstance(sub, tuple) and sub[0] == 'lateral':  # the lateral's share of the head conv's weights (+ its bias)
-            w = w[:, :sub[1]]
-        if op.get('share') is not None:  # a channel range of the stated conv; its (BN-folded) bias travels with ONE of the parts
-            lo, hi, with_bias = op['share'][:3]
-            w = w[:, lo:hi]
-            if len(op['share']) > 3:  # [running sum | feature]: identity block in front (Fuse2d over more than three features)
-                eye = torch.eye(cout, op['share'][3], dtype=w.dtype)[:, :, None, None]
-                w = torch.cat((eye, w), 1)
-            if not with_bias:
-                b = torch.zeros_like(b)
-        phase = isinstance(sub, tuple) and sub[0] in ('phase', 'scatter', 'blphase')
-        if isinstance(sub, tuple) and sub[0] == 'blphase':  # four k2 x k2 kernels on the low-resolution map (float64 sums)
-            from .subpixel import collapse_bilinear_taps
-            w = collapse_bilinear_taps(w).reshape(4, cout, cin, k, k)
-        elif phase:  # four 2 x 2 kernels on the low-resolution map (tap sums in float64, rounded to bf16 once)
-            from .subpixel import collapse_upsampled_taps
-            w = collapse_upsampled_taps(w[:, sub[1]:]).reshape(4, cout, cin, 2, 2)
-        c0 = plan.tensors[op['src0']]['c']
-        c0p = _pad(c0)
-        c1 = plan.tensors[op['src1']]['c'] if op['src1'] is not None else 0
-        cinp = c0p + (_pad(c1) if op['src1'] is not None else 0)
-        coutp = _pad(cout) if op['dst'] is not None else _pad32(cout)
-        if fp8:  # fold the input scales into the weights: the MFMA then accumulates real-valued units / weight scale
-            w = w.clone()
-            if groups == 1 and c1:
-                w[:, :c0] *= act_scales[op['src0']]
-                w[:, c0:] *= act_scales[op['src1']]
-            else:
-                w *= act_scales[op['src0']]
-        geo = _bundle_geometry(cin, cout, groups, KC)
-        if phase:
-            bundles, cin_b, cout_b = 4, cinp, coutp
-            kk = w.shape[-1]  # 2 (nearest phases) | k2 (bilinear phases)
-            dense = torch.zeros(4, coutp, cinp, kk, kk, dtype=torch.float64)
-            dense[:, :cout, :cin] = w
-            packed = dense.reshape(4, coutp, cinp // KC, KC, kk * kk).permute(0, 2, 4, 1, 3)
-            bias = None  # (partial sums; the lateral op of the triple adds the bias)
-            if fp8 and sub[0] == 'phase':  # (an all-zero bias keeps the bias / multiplier indices of the e4m3 kernel aligned)
-                bias = torch.zeros(4 * coutp, dtype=torch.float64)
-            if sub[0] in ('scatter', 'blphase'):  # one bias shared by the four phases
-                bias = torch.zeros(coutp, dtype=torch.float64)
-                bias[:cout] = b
-        elif geo is None:
-            dense = torch.zeros(coutp, cinp, k, k, dtype=torch.float64)
-            if groups == 1:
-                dense[:cout, :c0] = w[:, :c0]
-                if c1:
-                    dense[:cout, c0p:c0p + c1] = w[:, c0:]
-            else:  # densified grouped conv (block diagonal)
-                cig, cog = cin // groups, cout // groups
-                for g in range(groups):
-                    dense[g * cog:(g + 1) * cog, g * cig:(g + 1) * cig] = w[g * cog:(g + 1) * cog]
-            bundles, cin_b, cout_b = 1, cinp, coutp
-            packed = dense.reshape(1, coutp, cinp, k * k).permute(0, 3, 2, 1) if f32 else \
-                dense.reshape(1, coutp, cinp // KC, KC, k * k).permute(0, 2, 4, 1, 3)
-            bias = torch.zeros(coutp, dtype=torch.float64)
-            bias[:cout] = b
-        else:
-            bundles, cin_b, cout_b, gpb = geo
-            cig = cin // groups
-            dense = torch.zeros(bundles, cout_b, cin_b, k, k, dtype=torch.float64)
-            wg = w.reshape(bundles, gpb, cig, cig, k, k)  # [bundle, group-in-bundle, cout_g, cin_g, k, k]
-            for g in range(gpb):
-                dense[:, g * cig:(g + 1) * cig, g * cig:(g + 1) * cig] = wg[:, g]
-            packed = dense.reshape(bundles, cout_b, cin_b, k * k).permute(0, 3, 2, 1) if f32 else \
-                dense.reshape(bundles, cout_b, cin_b // KC, KC, k * k).permute(0, 2, 4, 1, 3)
-            bias = b.clone()
-        if fp8:
-            packed = packed.contiguous().reshape(bundles, -1, cout_b, KC)  # [bundle][item][cout][64]
-            wscale = (packed.abs().amax((1, 3)) / 448.).clamp_min(1e-30)      # [bundle][cout]
-            if isinstance(sub, tuple) and sub[0] == 'blphase':  # the four phases share ONE bias and ONE multiplier per channel
-                wscale = wscale.amax(0, keepdim=True).expand(bundles, -1)
-            codes = (packed / wscale[:, None, :, None]).to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
-            if codes.shape[1] % 2:  # the kernel's pipeline step holds two items
-                codes = torch.cat((codes, torch.zeros_like(codes[:, :1])), 1)
-            wparts.append(codes.contiguous().reshape(-1))
-            mparts.append((wscale[:1] if (isinstance(sub, tuple) and sub[0] == 'blphase') else wscale).reshape(-1).to(torch.float32))
-            wide = lambda t_: plan.tensors[t_].get('phases', 1) == 4  # bf16 partial sums: values, no code scale
-            op_scales[-1] = ((1. if wide(op['res']) else float(act_scales[op['res']])) if op['res'] is not None else 0.,
-                             (1. if wide(op['dst']) else 1. / float(act_scales[op['dst']])) if op['dst'] is not None else 0.)
-            if effective_weights is not None and (phase or (isinstance(sub, tuple) and sub[0] == 'lateral')):
-                effective_weights.append(dict(w=None, b=None))  # (a member op: the simulator follows the head op it restates)
-            elif effective_weights is not None:
-                dq = codes[:, :packed.shape[1]].view(torch.float8_e4m3fn).to(torch.float64) * wscale[:, None, :, None]
-                dq = dq.reshape(bundles, cin_b // KC, k * k, cout_b, KC).permute(0, 3, 1, 4, 2)  # [B][cout][chunk][64][tap]
-                dq = dq.reshape(bundles, cout_b, cin_b, k, k)
-                if geo is None:
-                    weff = torch.zeros_like(w)
-                    if groups == 1:
-                        weff[:, :c0] = dq[0, :cout, :c0] / act_scales[op['src0']]
-                        if c1:
-                            weff[:, c0:] = dq[0, :cout, c0p:c0p + c1] / act_scales[op['src1']]
-                    else:
-                        cig_, cog_ = cin // groups, cout // groups
-                        for g_ in range(groups):
-                            weff[g_ * cog_:(g_ + 1) * cog_] = dq[0, g_ * cog_:(g_ + 1) * cog_, g_ * cig_:(g_ + 1) * cig_]
-                        weff /= act_scales[op['src0']]
-                else:
-                    cig_ = cin // groups
-                    weff = torch.stack([dq[:, g_ * cig_:(g_ + 1) * cig_, g_ * cig_:(g_ + 1) * cig_] for g_ in range(gpb)], 1)
-                    weff = weff.reshape(cout, cig_, k, k) / act_scales[op['src0']]
-                effective_weights.append(dict(w=weff, b=b.clone()))
-        elif f32:
-            wparts.append(packed.contiguous().reshape(-1).to(wdt))
-        else:  # bf16: [bundle][item][cout][32]; the kernel's pipeline step holds two items -> pad an odd item count
-            packed = packed.contiguous().reshape(bundles, -1, cout_b, KC)
-            if packed.shape[1] % 2:
-                packed = torch.cat((packed, torch.zeros_like(packed[:, :1])), 1)
-            wparts.append(packed.contiguous().reshape(-1).to(wdt))
-        if bias is not None:
-            bparts.append(bias.to(torch.float32))
-        d.op = _lib.OP_CONV_DEFERRED if op.get('deferred') else _lib.OP_CONV
-        d.subpixel = {None: _lib.SUBPIXEL_NONE, 'head': _lib.SUBPIXEL_HEAD, 'phase': _lib.SUBPIXEL_PHASE,
-                      'lateral': _lib.SUBPIXEL_LATERAL, 'scatter': _lib.SUBPIXEL_SCATTER, 'blhead': _lib.SUBPIXEL_BL_HEAD,
-                      'blphase': _lib.SUBPIXEL_BL_PHASE, 'blframe': _lib.SUBPIXEL_BL_FRAME}[sub[0] if isinstance(sub, tuple) else sub]
-        d.src0 = op['src0']
-        d.src1 = -1 if op['src1'] is None else op['src1']
-        d.res = -1 if op['res'] is None else op['res']
-        d.dst = -1 if op['dst'] is None else op['dst']
-        d.up0, d.up1 = (2 if op['up0'] == 'bilinear' else int(op['up0'])), int(op['up1'])
-        d.res_up = 2 if op['res_up'] == 'shuffle' else int(op['res_up'])
-        d.c0_used = c0p if op['src1'] is not None else cinp
-        d.kh = d.kw = k
-        d.stride, d.pad = op['stride'], op['pad']
-        d.bundles, d.cin_b, d.cout_b = bundles, cin_b, cout_b
-        d.weight_offset, d.bias_offset = woff, (boff if bias is not None else -1)
-        d.act, d.act_scale = _ACT[op['act']], float(op['act_scale'])
-        d.out_index = -1 if op['out_index'] is None else op['out_index']
-        d.cout_real = cout
-        d.fuse_weight_offset = d.fuse_bias_offset = -1
-        d.fuse_cout = 0
-        woff += wparts[-1].numel() * wsz
-        if bias is not None:
-            boff += bparts[-1].numel()
-        # keep blob offsets 16-byte aligned
-        padw = (-wparts[-1].numel()) % (16 if fp8 else 8)
-        if padw:
-            wparts.append(torch.zeros(padw, dtype=torch.uint8 if fp8 else wdt))
-            woff += padw * wsz
-        if op.get('fuse'):
-            assert not f32, 'fused heads are a bf16-only feature'
-            fz = op['fuse']
-            w2 = state_dict[fz['w'] + 'weight'].detach().double().cpu().reshape(fz['cout'], cout)
-            b2 = state_dict[fz['w'] + 'bias'].detach().double().cpu()
-            W2 = torch.zeros(32, coutp, dtype=torch.float64)
-            W2[:fz['cout'], :cout] = w2
-            B2 = torch.zeros(32, dtype=torch.float64)
-            B2[:fz['cout']] = b2
-            wparts.append(W2.reshape(-1).to(torch.bfloat16).view(torch.uint8) if fp8 else W2.reshape(-1).to(torch.bfloat16))
-            bparts.append(B2.to(torch.float32))
-            if fp8:
-                mparts.append(torch.ones(32, dtype=torch.float32))  # keeps mult/bias indices aligned
-            d.fuse_weight_offset, d.fuse_bias_offset = woff, boff
-            d.fuse_cout, d.fuse_act, d.fuse_act_scale = fz['cout'], _ACT[fz['act']], float(fz['act_scale'])
-            d.cout_real = fz['cout']
-            woff += wparts[-1].numel() * (1 if fp8 else 2)
-            boff += bparts[-1].numel()
-    wblob = torch.cat(wparts).to(device)
-    bblob = torch.cat(bparts).to(device)
-    if fp8:  # multipliers live behind the biases in ONE float blob (cpn_op_desc.mult_offset); bias and multiplier
-        nb = bblob.numel()  # entries share their relative offsets
-        for d in ops:
-            if d.op == _lib.OP_CONV and d.bias_offset >= 0:
-                d.mult_offset = nb + d.bias_offset
-        allb = torch.cat((bblob, torch.cat(mparts).to(device)))
-        return tens, ops, wblob, allb, allb[nb:], op_scales
-    return tens, ops, wblob, bblob
-
-
 def reference_flops(plan: Plan, H, W, only=None):
     """2*MAC FLOPs of the reference graph per input (convs only, batch 1).  ``only``: optional
     predicate on the op dict (e.g. the backbone stack: ``lambda op: 'backbone' in op['w']``)."""
     total = 0.
     for op in plan.ops:
-        sub = op.get('sub')
+        kind = _sub_kind(op.get('sub'))
         if only is not None and op['op'] == 'conv' and not only(op):
             continue
-        if op['op'] != 'conv' or (isinstance(sub, tuple) and sub[0] != 'scatter'):  # (phase / lateral / bl ops restate their head)
+        if op['op'] != 'conv' or kind in _MEMBERS:  # (phase / lateral / bl ops restate their head)
             continue
-        t0 = plan.tensors[op['src0']]
-        scatter = isinstance(sub, tuple)  # stands for the reference's 3x3 conv over the x2-upsampled source
-        down_in = 1 if op['up0'] == 'bilinear' else t0['down'] // (2 if (op['up0'] or scatter) else 1)
+        scatter = kind == 'scatter'  # stands for the reference's 3x3 conv over the x2-upsampled source
+        down_in = _input_down(plan.tensors[op['src0']]['down'], op['up0'], scatter)
         ho, wo = H // (down_in * op['stride']), W // (down_in * op['stride'])
         f = 2. * ho * wo * op['cout'] * (op['cin'] // op['groups']) * (3 if scatter else op['k']) ** 2
         # the reference runs the UNet inner 1x1 after the upsample (4x the pixels), unet.py:213-218

@@ -1,4 +1,4 @@
-"""Sub-pixel decompositions of convolutions over x2-upsampled maps (host-side math of the packer, `graph.pack`).
+"""Sub-pixel decompositions of convolutions over x2-upsampled maps (host-side math of the packer, `pack.py`).
 
 The UNet decoder's first conv of every level reads ``cat(lateral, F.interpolate(top_down, mode='nearest'))``
 (celldetection/models/unet.py:207-230).  For the exact x2 case every output pixel ``(2i + py, 2j + px)`` sees the upsampled map
