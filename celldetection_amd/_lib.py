@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
 
@@ -161,6 +161,13 @@ _SIGNATURES = [
     ('cpn_props_compact_sort', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p]),
     ('cpn_props_finalise', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, POINTER(c_int32), c_int32, c_double, c_double,
                                           c_void_p, c_int64, c_void_p]),
+    ('cpn_overlay_bin_count', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_overlay_bin_fill', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                            c_void_p]),
+    ('cpn_overlay_paint', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, POINTER(ctypes.c_uint32), c_void_p]),
+    ('cpn_label_cmap', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                      POINTER(c_int32), c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -12,8 +12,9 @@
 // one round do not interact (if bbox_j meets E_k then j is a predecessor of k and k is not ready), so they read the
 // canvas and paint concurrently.  Rounds = longest chain of the predecessor relation (~10-20 for cells in NMS order).
 //
-// Polygon fill rule = OpenCV's FillEdgeCollection + boundary lines for integer vertices, restated (cv2 is not
-// available in the build image -- see oracle/labels_oracle.py, "parity unpinned"):
+// Polygon fill rule (on_line / lb_filled of csrc/polygon_fill.h, shared with csrc/overlay.hip) = OpenCV's FillEdgeCollection +
+// boundary lines for integer vertices, restated (cv2 is not available in the build image -- see oracle/labels_oracle.py,
+// "parity unpinned"):
 //   boundary: every edge drawn with the 8-connected LineIterator (left-to-right, err0 = dmaj - 2*dmin, diagonal step
 //             iff err < 0):  minor(t) = ceil((2*dmin*t - dmaj) / (2*dmaj));
 //   interior: scanline y takes the edges with y0 <= y < y1 (horizontal edges skipped), crossing x in 16.16 fixed point
@@ -25,6 +26,7 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "polygon_fill.h"
 
 namespace {
 
@@ -123,41 +125,6 @@ __global__ __launch_bounds__(256) void lb_ready_kernel(const int32_t *__restrict
 }
 
 // 3. paint: one workgroup (4 waves) per ready contour ------------------------------------------------------------------
-__device__ __forceinline__ bool on_line(int px, int py, int ax, int ay, int bx, int by) {
-    // 8-connected LineIterator from the left end point (left_to_right)
-    if (bx < ax) { int t = ax; ax = bx; bx = t; t = ay; ay = by; by = t; }
-    const int dx = bx - ax, dyv = by - ay, dy = dyv < 0 ? -dyv : dyv, sy = dyv < 0 ? -1 : 1;
-    if (dy <= dx) {  // x major
-        const int t = px - ax;
-        if (t < 0 || t > dx) return false;
-        const int m = dx == 0 ? 0 : (2 * dy * t - dx + 2 * dx - 1) / (2 * dx);  // ceil((2 dy t - dx) / (2 dx)), numerator > -2dx
-        return py == ay + sy * m;
-    }
-    const int t = (py - ay) * sy;  // y major (x is the minor axis and grows: left to right)
-    if (t < 0 || t > dy) return false;
-    const int m = (2 * dx * t - dy + 2 * dy - 1) / (2 * dy);
-    return px == ax + m;
-}
-
-// pixel (xx, yy) belongs to the filled polygon (boundary lines + scanline interior, see the header)
-__device__ __forceinline__ bool lb_filled(int xx, int yy, const int *px, const int *py, int S) {
-    bool set = false;
-    int n_lt = 0, n_le = 0;
-    for (int s = 0; s < S && !set; ++s) {
-        const int ax = px[s], ay = py[s], bx = px[s + 1 == S ? 0 : s + 1], by = py[s + 1 == S ? 0 : s + 1];
-        set = on_line(xx, yy, ax, ay, bx, by);
-        if (ay == by) continue;  // horizontal edges take no part in the scanline fill
-        const int ty = ay < by ? ay : by, tx = ay < by ? ax : bx, byy = ay < by ? by : ay;
-        if (yy < ty || yy >= byy) continue;
-        const long long ddx = ((long long) (bx - ax) * 65536ll) / (long long) (by - ay);  // C division: truncation
-        const long long xf = (long long) tx * 65536ll + (long long) (yy - ty) * ddx;
-        const int xr = (int) ((xf + 32768ll) >> 16);
-        n_lt += xr < xx;
-        n_le += xr <= xx;
-    }
-    return set || (n_lt & 1) || n_le > n_lt;
-}
-
 __global__ __launch_bounds__(256) void lb_paint_kernel(const int32_t *__restrict__ pts, const int32_t *__restrict__ boxes,
                                                       long K, int S, int H, int W, int gap,
                                                       const unsigned char *__restrict__ ready,

@@ -15,6 +15,7 @@ from . import ops as _ops
 __all__ = ['install_torchvision_nms', 'NAMESPACE']
 
 NAMESPACE = 'cpn_hip'
+OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap
 _lib_keepalive = []
 
 
@@ -122,6 +123,32 @@ def _(labels, properties, spacing_row, spacing_col):
     from . import region_props
     names, _ = region_props._column_names(region_props._resolve(tuple(p for p in properties.split(',') if p)), '-', 0)
     return labels.new_empty((torch.library.get_ctx().new_dynamic_size(), len(names)), dtype=torch.float64)
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::contours2overlay', mutates_args=(), device_types='cuda')
+def contours2overlay(contours: Tensor, colors: Tensor, height: int, width: int) -> Tensor:
+    """RGBA overlay image (celldetection/data/cpn.py:811-855, default arguments): contours [K, S, 2] and their uint8 colours
+    [K, 3] -> uint8 [height, width, 4]; see ``overlay.contours2overlay``."""
+    from . import overlay
+    return overlay.contours2overlay(contours, (height, width), colors=colors)
+
+
+@contours2overlay.register_fake
+def _(contours, colors, height, width):
+    return contours.new_empty((height, width, 4), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::label_cmap', mutates_args=(), device_types='cuda')
+def label_cmap(labels: Tensor, table: Tensor) -> Tensor:
+    """Colour-mapped label image (celldetection/visualization/cmaps.py:21-77 with ubyte=True): label image [H, W(, C)] and
+    float colours [n, 3 | 4] in [0, 1] -> uint8 [H, W, 4]; see ``overlay.label_cmap``."""
+    from . import overlay
+    return overlay.label_cmap(labels, colors=table, ubyte=True)
+
+
+@label_cmap.register_fake
+def _(labels, table):
+    return labels.new_empty(tuple(labels.shape[:2]) + (4,), dtype=torch.uint8)
 
 
 def install_torchvision_nms(force: bool = False) -> bool:

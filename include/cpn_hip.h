@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 18
+#define CPN_ABI_VERSION 19
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -607,6 +607,42 @@ int cpn_props_compact_sort(void *workspace, int64_t table_capacity, int32_t inte
 int cpn_props_finalise(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries,
                        const int32_t *properties, int32_t n_properties, double spacing_row, double spacing_col, int64_t *out,
                        int64_t out_columns, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Overlay images (cd.data.contours2overlay, celldetection/data/cpn.py:647-662,699-723,811-855, and cd.label_cmap(ubyte=True),
+ * celldetection/visualization/cmaps.py:21-77; both called from celldetection_scripts/cpn_inference.py:839-848;
+ * csrc/overlay.hip).  ABI 19.  out: uint8 [H][W][4] (r, g, b, a) on the device, 4-byte aligned.  H * W <= 2^31 - 1
+ * (CPN_E_UNSUPPORTED above).
+ * contours2overlay: points int32 [K][S][2] and boxes int32 [K][4] are the outputs of cpn_labels_prepare (1 <= S <= 512),
+ * colors uint8 [K][3].  Every contour is filled by the rule of the label rasteriser (csrc/polygon_fill.h); with n(p) contours
+ * covering pixel p and S(p) the per-channel sum of their colours, out(p) = (Sr / n, Sg / n, Sb / n, 255) (integer division)
+ * where n >= 1 and (0, 0, 0, 0) elsewhere.  The image is cut into tiles of CPN_OVERLAY_TILE x CPN_OVERLAY_TILE pixels,
+ * tiles_x = ceil(W / tile), tiles = tiles_x * ceil(H / tile), tile index = ty * tiles_x + tx.  No full-image intermediate.
+ *   bin_count: adds one to tile_count[t] (int32 [tiles], pre-zeroed) for every (contour, tile t its box meets).  Asynchronous.
+ *   bin_fill:  tile_begin = int32 [tiles + 1], the exclusive scan of tile_count with the total (= pairs) at the end (the
+ *              caller scans); cursor = int32 [tiles], pre-zeroed; writes the contour index of every pair into
+ *              list[tile_begin[t] ..] (int32 [pairs]; the order within a tile is unspecified: the result does not depend on
+ *              it).  Asynchronous.
+ *   paint:     one workgroup per tile sums the colours of the contours of its list in LDS and writes every pixel of the
+ *              image exactly once.  max_overlap: one device word, pre-zeroed, receives the largest n(p); with
+ *              max_overlap_host != NULL it is copied there and the stream synchronised.  The sums are exact for
+ *              n <= (2^32 - 1) / 255.  K = 0 (tile_begin all zero) writes zeros.
+ * label_cmap: labels int32 [pixels][channels] on the device, channel-interleaved; table uint8 [rows][4] on the device,
+ * 4-byte aligned, row 0 = the colour of label 0, rows >= 2.  Label v > 0 takes row v % (rows - 1) + 1.  reduce == 0 (channels
+ * must be 1): out = the row.  reduce != 0: float32, in this order and without contraction: den = float(sum_c a_c) + 1e-12f;
+ * for c = 0 .. channels - 1: w = a_c / den (correctly rounded), acc_j = acc_j + w * col_cj for j = r, g, b, a; out_j = acc_j
+ * truncated.  flag: one device word, pre-zeroed, becomes non-zero when a label is negative (such pixels take row 0); with
+ * flag_host != NULL it is copied there and the stream synchronised.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_OVERLAY_TILE 32
+int cpn_overlay_bin_count(const int32_t *boxes, int64_t K, int32_t H, int32_t W, int32_t *tile_count, void *stream);
+int cpn_overlay_bin_fill(const int32_t *boxes, int64_t K, int32_t H, int32_t W, const int32_t *tile_begin, int32_t *cursor,
+                         int32_t *list, int64_t pairs, void *stream);
+int cpn_overlay_paint(const int32_t *points, const int32_t *boxes, const uint8_t *colors, int64_t K, int32_t S, int32_t H,
+                      int32_t W, const int32_t *tile_begin, const int32_t *list, uint8_t *out, uint32_t *max_overlap,
+                      uint32_t *max_overlap_host, void *stream);
+int cpn_label_cmap(const int32_t *labels, int64_t pixels, int32_t channels, int32_t reduce, const uint8_t *table, int32_t rows,
+                   uint8_t *out, int32_t *flag, int32_t *flag_host, void *stream);
 
 #ifdef __cplusplus
 }
