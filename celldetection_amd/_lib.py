@@ -10,9 +10,9 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
-E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
+E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_INTERNAL = -1, -2, -3, -4
 
 OP_INPUT, OP_CONV, OP_MAXPOOL, OP_BILINEAR, OP_CONV_DEFERRED, OP_INPUT_STEM, OP_STEM7, OP_CONV_PAIR, OP_CONV_BRIDGE, OP_ACT = \
     0, 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -168,6 +168,17 @@ _SIGNATURES = [
                                          c_void_p, c_void_p, POINTER(ctypes.c_uint32), c_void_p]),
     ('cpn_label_cmap', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                       POINTER(c_int32), c_void_p]),
+    ('cpn_contours_workspace_bytes', c_int64, [c_int64]),
+    ('cpn_contours_components', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, POINTER(c_int64),
+                                               c_void_p]),
+    ('cpn_contours_table', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_int64, POINTER(c_int64), c_void_p]),
+    ('cpn_contours_count', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    ('cpn_contours_write', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
+    ('cpn_resample_contours', ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p,
+                                             c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -15,7 +15,7 @@ from . import ops as _ops
 __all__ = ['install_torchvision_nms', 'NAMESPACE']
 
 NAMESPACE = 'cpn_hip'
-OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap
+OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap / .labels2contours_packed / .resample_contours
 _lib_keepalive = []
 
 
@@ -149,6 +149,36 @@ def label_cmap(labels: Tensor, table: Tensor) -> Tensor:
 @label_cmap.register_fake
 def _(labels, table):
     return labels.new_empty(tuple(labels.shape[:2]) + (4,), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::labels2contours_packed', mutates_args=(), device_types='cuda')
+def labels2contours_packed(labels: Tensor, raise_fragmented: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """Contours of a label image (celldetection/data/cpn.py:93-144, RETR_EXTERNAL / CHAIN_APPROX_NONE): label image [H, W, C] ->
+    ids int32 [K], offsets int64 [K + 1], points int32 [P, 2]; fragmented objects raise or are skipped (flagging in place is
+    left to the Python function); see ``label_contours.labels2contours_packed``."""
+    from . import label_contours
+    return label_contours.labels2contours_packed(labels, raise_fragmented=raise_fragmented)
+
+
+@labels2contours_packed.register_fake
+def _(labels, raise_fragmented):
+    ctx = torch.library.get_ctx()
+    k, p = ctx.new_dynamic_size(), ctx.new_dynamic_size()
+    return (labels.new_empty((k,), dtype=torch.int32), labels.new_empty((k + 1,), dtype=torch.int64),
+            labels.new_empty((p, 2), dtype=torch.int32))
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::resample_contours', mutates_args=(), device_types='cuda')
+def resample_contours(points: Tensor, offsets: Tensor, num: int, close: bool, epsilon: float) -> Tensor:
+    """Equidistant points on packed contours (celldetection/data/misc.py:371-405): points [P, 2], offsets int64 [K + 1] ->
+    float64 [K, num, 2]; see ``label_contours.resample_contours_packed``."""
+    from . import label_contours
+    return label_contours.resample_contours_packed(points, offsets, num, close, epsilon)
+
+
+@resample_contours.register_fake
+def _(points, offsets, num, close, epsilon):
+    return points.new_empty((offsets.shape[0] - 1, num, 2), dtype=torch.float64)
 
 
 def install_torchvision_nms(force: bool = False) -> bool:

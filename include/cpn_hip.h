@@ -24,11 +24,12 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 19
+#define CPN_ABI_VERSION 20
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
 #define CPN_E_WORKSPACE (-3)
+#define CPN_E_INTERNAL (-4) /* a bound that holds by construction was reached (ABI 20: the contour trace) */
 
 const char *cpn_last_error(void);
 int cpn_abi_version(void);
@@ -643,6 +644,56 @@ int cpn_overlay_paint(const int32_t *points, const int32_t *boxes, const uint8_t
                       uint32_t *max_overlap_host, void *stream);
 int cpn_label_cmap(const int32_t *labels, int64_t pixels, int32_t channels, int32_t reduce, const uint8_t *table, int32_t rows,
                    uint8_t *out, int32_t *flag, int32_t *flag_host, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Contours of label images (cd.data.labels2contours / labels2contour_list, celldetection/data/cpn.py:93-144, and
+ * cd.data.resample_contours, celldetection/data/misc.py:371-405; csrc/label_contours.hip, csrc/contour_trace.h).  ABI 20.
+ * labels: int32 [H][W][channels] on the device, channel-interleaved, channels <= 65535, H * W <= 2^31 - 1 (CPN_E_UNSUPPORTED
+ * above).  Rule: an object is a pair (channel, value v > 0); values <= 0 take no part.  Its components are the 8-connected sets
+ * of pixels of that channel holding v.  An object with exactly one component yields one contour: Suzuki-Abe border following of
+ * the outer border as cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) does it -- start at the raster-first pixel (smallest y,
+ * then smallest x); first search clockwise on screen from the west neighbour; every further search counter-clockwise, starting
+ * after the pixel just left; every visit is a point (one-pixel-wide parts appear once per passage); stop when the start pixel
+ * is re-entered from the first found neighbour; a single pixel gives its point twice; points are (x, y) in image coordinates.
+ * An object with more than one component is fragmented and yields no contour.  Departure from cv2: a component that lies in a
+ * hole of another component of the same value counts as a component.  Contours come by ascending value; of a value that is
+ * unfragmented in several channels the highest such channel is returned.
+ * All calls for one image use one workspace of cpn_contours_workspace_bytes(entries) bytes, entries >= the root count
+ * (cpn_contours_workspace_bytes(0) suffices for cpn_contours_components), and the same roots image.
+ *   components: roots = int32 [channels][H][W]: -1 where the value is <= 0, otherwise the index y * W + x of the raster-first
+ *               pixel of the pixel's component (tiles of CPN_CONTOURS_TILE x CPN_CONTOURS_TILE pixels in LDS, then the seams with
+ *               agent-scope atomics, then a flattening pass).  status_host[0] = components of all channels.  Synchronises.
+ *   table:      entries = that count.  Replaces the word of every root in `roots` by -2 - (an internal slot); writes table =
+ *               int32 [4][entries]: rows value, channel, root index, pixel count of the K contours to return, in their order
+ *               (only the first K columns are written), and frag_values = int32 [entries]: the value of every component of a
+ *               fragmented object, 0 elsewhere.  status_host[0] = K, [1] = components of fragmented objects.  Synchronises.
+ *   count:      chan / root / npix = rows 1 .. 3 of the table.  One lane follows one border and counts its points: lengths =
+ *               int64 [K], offsets = int64 [K + 1] (offsets[0] = 0, then the running sum).  status_host[0] = offsets[K] = all
+ *               points.  A trace is capped at 8 * npix points (a pixel is entered from at most 8 directions); reaching the cap
+ *               returns CPN_E_INTERNAL.  Synchronises.
+ *   write:      the same traces again; points = int32 [offsets[K]][2] as (x, y).  A trace whose length differs from the counted
+ *               one returns CPN_E_INTERNAL; no store goes beyond the contour's own range.  Synchronises.
+ * resample_contours: points = double [total_points][2], contour k = points[offsets[k] .. offsets[k + 1]) with at least one
+ * segment each (close != 0: the last point is joined to the first).  cumsum = double [total_points + K] scratch.  out = double
+ * [K][num][2].  In fp64, in this order, without contraction: dt_i = sqrt(dx^2 + dy^2) + epsilon; cumsum = the running sum of
+ * dt taken sequentially in index order; t_j = j * (cumsum_last / num); i = the first index with t_j <= cumsum_i; alpha =
+ * (t_j - cumsum_(i-1)) / dt_i (cumsum_(-1) = 0); out_j = p_i * (1 - alpha) + p_(i+1) * alpha.  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_CONTOURS_TILE 32
+int64_t cpn_contours_workspace_bytes(int64_t entries);
+int cpn_contours_components(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t *roots, void *workspace,
+                            int64_t workspace_bytes, int64_t *status_host, void *stream);
+int cpn_contours_table(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t *roots, int64_t entries,
+                       int32_t *table, int32_t *frag_values, void *workspace, int64_t workspace_bytes, int64_t *status_host,
+                       void *stream);
+int cpn_contours_count(const int32_t *roots, int32_t channels, int32_t H, int32_t W, int64_t K, const int32_t *chan,
+                       const int32_t *root, const int32_t *npix, int64_t *lengths, int64_t *offsets, void *workspace,
+                       int64_t workspace_bytes, int64_t *status_host, void *stream);
+int cpn_contours_write(const int32_t *roots, int32_t channels, int32_t H, int32_t W, int64_t K, const int32_t *chan,
+                       const int32_t *root, const int32_t *npix, const int64_t *offsets, int32_t *points, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int cpn_resample_contours(const double *points, const int64_t *offsets, int64_t K, int64_t total_points, int32_t num,
+                          int32_t close, double epsilon, double *cumsum, double *out, void *stream);
 
 #ifdef __cplusplus
 }
