@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_INTERNAL = -1, -2, -3, -4
 
@@ -179,6 +179,9 @@ _SIGNATURES = [
                                           c_void_p, c_void_p, c_int64, c_void_p]),
     ('cpn_resample_contours', ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p,
                                              c_void_p]),
+    ('cpn_efd_workspace_bytes', c_int64, [c_int64, c_int64, c_int32]),
+    ('cpn_efd', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_int64, c_void_p,
+                               c_void_p, POINTER(c_int64), c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -37,6 +37,8 @@ SOURCES = {
     # integer components and border following; the fp64 resampling is defined by its order of operations: no FMA contraction
     # (fp64 sqrt and division are correctly rounded as they stand)
     'label_contours.hip': ['-ffp-contract=off'],
+    # fp64 sums whose result is defined by their order of operations (csrc/efd_chunks.h): no FMA contraction
+    'contour_fourier.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -45,7 +47,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

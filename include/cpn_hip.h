@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 20
+#define CPN_ABI_VERSION 21
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -694,6 +694,48 @@ int cpn_contours_write(const int32_t *roots, int32_t channels, int32_t H, int32_
                        int64_t workspace_bytes, void *stream);
 int cpn_resample_contours(const double *points, const int64_t *offsets, int64_t K, int64_t total_points, int32_t num,
                           int32_t close, double epsilon, double *cumsum, double *out, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Elliptic Fourier descriptors of contours (cd.data.cpn.efd / contours2fourier, celldetection/data/cpn.py:23-90, 213-227;
+ * csrc/contour_fourier.hip, csrc/efd_chunks.h).  ABI 21.
+ * points: int32 or double [P][2] as (x, y) on the device (points_dtype = CPN_EFD_POINTS_*), read as they are; offsets: int64
+ * [K + 1] on the device, contour k = points[offsets[k] .. offsets[k + 1]) with at least one point.  The call first checks on the
+ * device that offsets starts at 0, ends at P and grows by at least one per contour, and returns CPN_E_INVALID otherwise; every
+ * index into points, workspace and outputs is derived from offsets.  1 <= order <= CPN_EFD_MAX_ORDER.
+ * Rule.  A contour of n points is closed if |first - last| <= 1e-8 + 1e-5 |last| holds for both coordinates (numpy's allclose
+ * with b = last).  close_mode: CPN_EFD_CLOSE_NONE takes the contours as they are (N = n - 1 segments); the contours that are not
+ * closed are counted in status_host[0], and when there is one nothing is computed (the caller raises).  CPN_EFD_CLOSE_ALL
+ * appends the first point to every contour (N = n), CPN_EFD_CLOSE_EACH to the contours that are not closed.  For i = 0 .. N - 1:
+ * dx_i, dy_i = the point differences, dt_i = sqrt(dx_i^2 + dy_i^2) + epsilon, t_0 = 0, t_(i+1) = t_i + dt_i, T = t_N.  For k = 1 ..
+ * order with phi_(k,i) = k * (2 pi t_i / T) and C_k = T / (2 k^2 pi^2):
+ *   coefficients[K][order][4]: C_k * (sum dx_i/dt_i dcos, sum dx_i/dt_i dsin, sum dy_i/dt_i dcos, sum dy_i/dt_i dsin) with
+ *   dcos = cos phi_(k,i+1) - cos phi_(k,i), dsin likewise;
+ *   locations[K][2]: first point + (a0, c0), a0 = (1/T) sum [dx_i/(2 dt_i) (t_(i+1)^2 - t_i^2) + (X_i - dx_i/dt_i t_(i+1)) dt_i],
+ *   X_i = sum_(j<=i) dx_j (taken as x_(i+1) - x_0), c0 the same with y.
+ * N = 0 (one point) gives coefficients 0 and location NaN; N = 1 with T = epsilon (the doubled point of labels2contours) gives
+ * coefficients 0 and exactly that point.  All arithmetic is float64 without contraction.  Order of summation: a chunk is up to
+ * CPN_EFD_CHUNK consecutive segments counted from the contour's own first segment; csrc/efd_chunks.h fixes the order within a
+ * chunk and across chunks.  It depends on the contour alone: a result is bit-identical from run to run and wherever the
+ * contour lies among others.  No floating-point atomics.
+ * workspace: cpn_efd_workspace_bytes(K, P, order) bytes on the device (it grows with (P + K) / CPN_EFD_CHUNK * order: room for
+ * the partial sums of contours of more than one chunk).  status_host: int64 [CPN_EFD_STATUS_WORDS] on the host: [0] contours
+ * that are not closed, [1] chunks of contours of more than one chunk; with CPN_EFD_TIMED or-ed into close_mode [2 .. 6] are the
+ * nanoseconds (HIP events) of: checks and work list, single-chunk contours, chunk sums and bases, partial sums, finish.
+ * Synchronises (the checks are read back before anything else is launched).  K = 0 (P must be 0) does nothing.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_EFD_CHUNK 256
+#define CPN_EFD_MAX_ORDER 64
+#define CPN_EFD_POINTS_I32 0
+#define CPN_EFD_POINTS_F64 1
+#define CPN_EFD_CLOSE_NONE 0
+#define CPN_EFD_CLOSE_ALL 1
+#define CPN_EFD_CLOSE_EACH 2
+#define CPN_EFD_TIMED 256
+#define CPN_EFD_STATUS_WORDS 8
+int64_t cpn_efd_workspace_bytes(int64_t K, int64_t P, int32_t order);
+int cpn_efd(const void *points, int32_t points_dtype, const int64_t *offsets, int64_t K, int64_t P, int32_t order, double epsilon,
+            int32_t close_mode, void *workspace, int64_t workspace_bytes, double *coefficients_f64, double *locations_f64,
+            int64_t *status_host, void *stream);
 
 #ifdef __cplusplus
 }
