@@ -7,7 +7,7 @@ loop.  Everything computes in hand-written HIP kernels behind the C ABI of ``lib
 """
 from . import cpn as models  # ``cd.models.CpnResNeXt101UNet`` -> ``celldetection_amd.models.CpnResNeXt101UNet``
 from . import (flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, ops, overlay, preprocess, region_props, synth,
-               util)
+               targets, util)
 from .flat_labels import resolve_label_channels
 from .fourier import contours2fourier, efd, labels2fourier
 from .h5 import from_h5, to_h5
@@ -17,6 +17,7 @@ from .label_contours import labels2contour_list as labels2contours  # ``cd.data.
 from .label_contours import resample_contours
 from .labels import contours2labels
 from .overlay import contours2overlay, label_cmap, random_colors_hsv
+from .targets import CPNTargetGenerator, filter_instances_, labels2distances, mask_labels_by_distance_
 from .util import (dict2model, fetch_model, get_tiling_slices, load_model, model2dict, save_fetchable_model)
 
 __version__ = '0.1.0'
@@ -24,4 +25,4 @@ __all__ = ['models', 'ops', 'util', 'synth', 'inference', 'labels', 'contours2la
            'model2dict', 'get_tiling_slices', 'instance_eval', 'LabelMatcher', 'LabelMatcherList', 'flat_labels',
            'resolve_label_channels', 'region_props', 'region_properties', 'labels2property_table', 'overlay', 'contours2overlay',
            'label_cmap', 'random_colors_hsv', 'label_contours', 'labels2contours', 'resample_contours', 'fourier', 'efd', 'contours2fourier',
-           'labels2fourier']
+           'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator']

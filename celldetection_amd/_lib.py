@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CPN_HIP_LIB') or os.path.join(HERE, 'libcpn_hip.so')  # env: kernel A/B tuning only
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 PRECISION_BF16, PRECISION_F32, PRECISION_FP8 = 0, 1, 2
 E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_INTERNAL = -1, -2, -3, -4
 
@@ -182,6 +182,18 @@ _SIGNATURES = [
     ('cpn_efd_workspace_bytes', c_int64, [c_int64, c_int64, c_int32]),
     ('cpn_efd', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_int64, c_void_p,
                                c_void_p, POINTER(c_int64), c_void_p]),
+    ('cpn_label_distances_workspace_bytes', c_int64, [c_int32, c_int32]),
+    ('cpn_label_distances_table_bytes', c_int64, [c_int64]),
+    ('cpn_label_distances_classify', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                                    POINTER(c_int64), c_void_p]),
+    ('cpn_label_distances_step', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                                POINTER(c_int64), c_void_p]),
+    ('cpn_label_distances_reduce', ctypes.c_int, [c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64),
+                                                  c_void_p]),
+    ('cpn_label_distances_finalise', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    ('cpn_label_distances_mask', ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    ('cpn_label_remap', ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -39,6 +39,8 @@ SOURCES = {
     'label_contours.hip': ['-ffp-contract=off'],
     # fp64 sums whose result is defined by their order of operations (csrc/efd_chunks.h): no FMA contraction
     'contour_fourier.hip': ['-ffp-contract=off'],
+    # integer chamfer relaxation; the float32 normalisation is one IEEE division per pixel: correctly rounded, no contraction
+    'label_distances.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)

@@ -15,7 +15,7 @@ from . import ops as _ops
 __all__ = ['install_torchvision_nms', 'NAMESPACE']
 
 NAMESPACE = 'cpn_hip'
-OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap / .labels2contours_packed / .resample_contours
+OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap / .labels2contours_packed / .resample_contours / .labels2distances
 _lib_keepalive = []
 
 
@@ -179,6 +179,20 @@ def resample_contours(points: Tensor, offsets: Tensor, num: int, close: bool, ep
 @resample_contours.register_fake
 def _(points, offsets, num, close, epsilon):
     return points.new_empty((offsets.shape[0] - 1, num, 2), dtype=torch.float64)
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::labels2distances', mutates_args=(), device_types='cuda')
+def labels2distances(labels: Tensor, distance_type: int, per_instance: bool, protected_size: int) -> tuple[Tensor, Tensor]:
+    """Distance map of a label image (celldetection/data/cpn.py:432-497, overlap_zero=True): label image [H, W(, C)] -> distances
+    float32 [H, W] and the labels [H, W, C] with overlap pixels set to -1; see ``targets.labels2distances``."""
+    from . import targets
+    return targets.labels2distances(labels, distance_type=distance_type, per_instance=per_instance, protected_size=protected_size)
+
+
+@labels2distances.register_fake
+def _(labels, distance_type, per_instance, protected_size):
+    return (labels.new_empty(tuple(labels.shape[:2]), dtype=torch.float32),
+            labels.new_empty(tuple(labels.shape[:2]) + (labels.shape[2] if labels.ndim == 3 else 1,)))
 
 
 def install_torchvision_nms(force: bool = False) -> bool:

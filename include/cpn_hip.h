@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 21
+#define CPN_ABI_VERSION 22
 
 #define CPN_E_INVALID (-1)
 #define CPN_E_UNSUPPORTED (-2)
@@ -736,6 +736,60 @@ int64_t cpn_efd_workspace_bytes(int64_t K, int64_t P, int32_t order);
 int cpn_efd(const void *points, int32_t points_dtype, const int64_t *offsets, int64_t K, int64_t P, int32_t order, double epsilon,
             int32_t close_mode, void *workspace, int64_t workspace_bytes, double *coefficients_f64, double *locations_f64,
             int64_t *status_host, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * CPN training targets (cd.data.labels2distances / mask_labels_by_distance_, celldetection/data/cpn.py:424-497, and
+ * cd.data.filter_instances_, celldetection/data/segmentation.py:67-103; csrc/label_distances.hip).  ABI 22.
+ * labels: int32 [H][W][channels] on the device, channel-interleaved; H, W <= 32768 (CPN_E_UNSUPPORTED above): every distance
+ * fits uint32.  owner(p) = the one positive value at p when exactly one channel is > 0, otherwise 0.  distance_type selects the
+ * weights of OpenCV's 3 x 3 chamfer transform in 16-bit fixed point (HV straight, DIAG diagonal): CPN_DIST_L2 (62587, 89738) =
+ * round((0.955, 1.3693) * 2^16), CPN_DIST_L1 (1, 2) * 2^16, CPN_DIST_C (1, 1) * 2^16.  t(p) = min over zero pixels q of
+ * DIAG * min(|dx|, |dy|) + HV * (max - min).  per_instance != 0: a zero pixel for p is every pixel whose owner differs from
+ * owner(p), pixels outside the image included.  per_instance == 0: a zero pixel is a pixel with owner 0 inside the image.
+ * All calls for one image use the same workspace, distance_type and per_instance.  Integer arithmetic until finalise, no
+ * floating-point atomics: every result is bit-identical from run to run.
+ *   workspace_bytes: counters, the owner image, two t images and the tile flags (0: H or W out of range).
+ *   table_bytes:     the hash table (key, n, tmax) of `table_capacity` slots, a power of two from 64 to 2^28 (0 otherwise).
+ *   classify:        owner and the seed of t (the cheapest step to an 8-neighbour that is a zero pixel; none: 2^32 - 1); marks
+ *                    the 32 x 32 tiles that hold owner pixels.  status_host[0] = pixels with owner 0.  Synchronises the stream,
+ *                    unless status_host is NULL.
+ *   step:            `steps` (1 .. CPN_LABEL_DISTANCES_MAX_STEPS) synchronous steps t(p) = min(t(p), t(n) + w) over the
+ *                    8-neighbours n that are no zero pixel for p, on every tile with owner pixels next to a change of the
+ *                    previous call (`launch` counts the calls for this image from 0; call 0 runs all of them).
+ *                    status_host[0] = pixels changed, [1] = tiles run.  0 pixels: the fixed point, t is final.
+ *                    Synchronises the stream, unless status_host is NULL.
+ *   reduce:          zeroes the table and accumulates per owner value n = pixel count and tmax = max t (per tile in LDS, then
+ *                    one set of integer atomics per tile and value).  status_host[0] = inserts that found no slot (> 0: repeat
+ *                    with a larger table).  Synchronises the stream, unless status_host is NULL.
+ *   finalise:        distances float32 [H][W]: d = float32(t) * 2^-16; per_instance != 0: n > protected_size and tmax > 0:
+ *                    d = d / (float32(tmax) * 2^-16); per_instance == 0: d = d / max(float32(tmax) * 2^-16, 1e-6f) (IEEE division,
+ *                    no contraction); d clipped to [0, 1]; 0 where owner is 0.  labels_out int32 [H][W][channels] = labels with
+ *                    every channel of an overlap pixel (more than one channel > 0) set to -1.  Asynchronous.
+ *   mask:            in place on labels int32 [pixels][channels]: a pixel with any channel > 0 and d <= max_bg_dist gets all
+ *                    channels 0; then a pixel with max_bg_dist < d < min_fg_dist gets all channels -1.  reduced: NULL or int32
+ *                    [pixels], receives the channel maximum of the result.  Asynchronous.
+ * cpn_label_remap: in place on int32 [elements]: an element equal to keys[i] (int32 [entries], ascending, distinct) becomes
+ * values[i]; other elements stay.  One binary search per element.  Asynchronous.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_LABEL_DISTANCES_MAX_STEPS 8
+#define CPN_DIST_L1 1
+#define CPN_DIST_L2 2
+#define CPN_DIST_C 3
+int64_t cpn_label_distances_workspace_bytes(int32_t H, int32_t W);
+int64_t cpn_label_distances_table_bytes(int64_t table_capacity);
+int cpn_label_distances_classify(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t distance_type,
+                                 int32_t per_instance, void *workspace, int64_t workspace_bytes, int64_t *status_host,
+                                 void *stream);
+int cpn_label_distances_step(int32_t H, int32_t W, int32_t steps, int32_t distance_type, int32_t per_instance, int32_t launch,
+                             void *workspace, int64_t workspace_bytes, int64_t *status_host, void *stream);
+int cpn_label_distances_reduce(int32_t H, int32_t W, void *workspace, int64_t workspace_bytes, void *table,
+                               int64_t table_capacity, int64_t *status_host, void *stream);
+int cpn_label_distances_finalise(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t per_instance,
+                                 int32_t protected_size, void *workspace, int64_t workspace_bytes, const void *table,
+                                 int64_t table_capacity, float *distances, int32_t *labels_out, void *stream);
+int cpn_label_distances_mask(int32_t *labels, int32_t channels, int64_t pixels, const float *distances, float max_bg_dist,
+                             float min_fg_dist, int32_t *reduced, void *stream);
+int cpn_label_remap(int32_t *labels, int64_t elements, const int32_t *keys, const int32_t *values, int32_t entries, void *stream);
 
 #ifdef __cplusplus
 }
