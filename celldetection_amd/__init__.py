@@ -6,13 +6,14 @@ loop.  Everything computes in hand-written HIP kernels behind the C ABI of ``lib
 (``include/cpn_hip.h``); there is no CPU fallback.
 """
 from . import cpn as models  # ``cd.models.CpnResNeXt101UNet`` -> ``celldetection_amd.models.CpnResNeXt101UNet``
-from . import (flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, ops, overlay, preprocess, region_props, synth,
+from . import (flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, ops, overlay, preprocess, region_props, shape_props, synth,
                targets, util)
 from .flat_labels import resolve_label_channels
 from .fourier import contours2fourier, efd, labels2fourier
 from .h5 import from_h5, to_h5
 from .instance_eval import LabelMatcher, LabelMatcherList
 from .region_props import labels2property_table, region_properties
+from .shape_props import shape_properties
 from .label_contours import labels2contour_list as labels2contours  # ``cd.data.labels2contours`` is that function
 from .label_contours import resample_contours
 from .labels import contours2labels
@@ -23,6 +24,6 @@ from .util import (dict2model, fetch_model, get_tiling_slices, load_model, model
 __version__ = '0.1.0'
 __all__ = ['models', 'ops', 'util', 'synth', 'inference', 'labels', 'contours2labels', 'preprocess', 'h5', 'to_h5', 'from_h5', 'fetch_model', 'load_model', 'save_fetchable_model', 'dict2model',
            'model2dict', 'get_tiling_slices', 'instance_eval', 'LabelMatcher', 'LabelMatcherList', 'flat_labels',
-           'resolve_label_channels', 'region_props', 'region_properties', 'labels2property_table', 'overlay', 'contours2overlay',
+           'resolve_label_channels', 'region_props', 'region_properties', 'labels2property_table', 'shape_props', 'shape_properties', 'overlay', 'contours2overlay',
            'label_cmap', 'random_colors_hsv', 'label_contours', 'labels2contours', 'resample_contours', 'fourier', 'efd', 'contours2fourier',
            'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator']

@@ -30,6 +30,9 @@ PROP_NAMES = ('label', 'bbox', 'num_pixels', 'area', 'area_bbox', 'extent', 'equ
               'eccentricity', 'orientation', 'intensity_mean', 'intensity_min', 'intensity_max')
 PROP_CODES = {name: code for code, name in enumerate(PROP_NAMES)}
 PROPS_U8, PROPS_I16, PROPS_I32 = 0, 1, 2
+# shape properties (CPN_SHAPE_* of include/cpn_hip.h), in code order
+SHAPE_NAMES = ('label', 'num_pixels', 'perimeter', 'perimeter_crofton', 'euler_number', 'area_convex', 'solidity')
+SHAPE_CODES = {name: code for code, name in enumerate(SHAPE_NAMES)}
 
 
 class TensorDesc(Structure):
@@ -161,6 +164,15 @@ _SIGNATURES = [
     ('cpn_props_compact_sort', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p]),
     ('cpn_props_finalise', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, POINTER(c_int32), c_int32, c_double, c_double,
                                           c_void_p, c_int64, c_void_p]),
+    ('cpn_shape_workspace_bytes', c_int64, [c_int64]),
+    ('cpn_shape_columns', c_int32, [POINTER(c_int32), c_int32]),
+    ('cpn_shape_heights', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p]),
+    ('cpn_shape_accumulate', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int64, c_void_p,
+                                            c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    ('cpn_shape_hull_scratch_bytes', c_int64, [c_int64, c_int64]),
+    ('cpn_shape_hull', ctypes.c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    ('cpn_shape_finalise', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, POINTER(c_int32), c_int32,
+                                          c_double, c_double, c_void_p, c_int64, c_void_p]),
     ('cpn_overlay_bin_count', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     ('cpn_overlay_bin_fill', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                             c_void_p]),

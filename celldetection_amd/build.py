@@ -31,6 +31,8 @@ SOURCES = {
     'flat_labels.hip': [],  # integer only
     # integer accumulation; the fp64 finalisation is defined by its order of operations: no FMA contraction
     'region_props.hip': ['-ffp-contract=off'],
+    # integer counts; the fp64 finalisation is defined by its order of operations: no FMA contraction
+    'shape_props.hip': ['-ffp-contract=off'],
     # integer overlay sums; the float32 colour-map reduction is defined by its order of operations: separate multiply and add,
     # correctly rounded division
     'overlay.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
@@ -49,7 +51,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'props_table.h', 'hull_count.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -33,29 +33,14 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "props_table.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
 constexpr int RP_MAX_C = 11;         // label channels
-constexpr int RP_MAX_K = 4;          // intensity channels
 constexpr int RP_TILE_H = 32, RP_TILE_W = 64, RP_PPT = 8;
 constexpr int RP_LDS_SLOTS = 128, RP_LDS_PROBE = 16;
-constexpr u64 RP_MAX_PROBE = 4096;   // probes before an insert reports overflow
 constexpr int RP_MAX_PROPS = 64;
-constexpr int64_t RP_HEAD_BYTES = 64;  // counters in front of the workspace: [0] overflow, [1] entries, [2] cursor
-constexpr int64_t RP_MAX_CAPACITY = (int64_t) 1 << 28;  // slot numbers take 28 bits of a sort key
-
-struct Table {
-    u64 *keys, *n, *sums;      // [cap], [cap], [5][cap]
-    uint32_t *box;             // [4][cap]: 65536 - rmin, 65536 - cmin, rmax + 1, cmax + 1
-    i64 *isum;                 // [K][cap]
-    uint32_t *imin, *imax;     // [K][cap], mirrored / biased
-    u64 cap, mask;
-    u64 *overflow;
-};
 
 struct Run {  // what one run or one LDS slot adds to a row
     unsigned n;
@@ -64,33 +49,6 @@ struct Run {  // what one run or one LDS slot adds to a row
     i64 isum[RP_MAX_K];
     uint32_t imin[RP_MAX_K], imax[RP_MAX_K];
 };
-
-inline int64_t rp_row_bytes(int K) { return 8 + 8 + 40 + 16 + (int64_t) K * 16; }
-
-Table rp_table(void *workspace, int64_t cap, int K) {
-    Table t;
-    char *w = (char *) workspace;
-    t.overflow = (u64 *) w;
-    w += RP_HEAD_BYTES;
-    t.keys = (u64 *) w;      w += cap * 8;
-    t.n = (u64 *) w;         w += cap * 8;
-    t.sums = (u64 *) w;      w += cap * 40;
-    t.isum = (i64 *) w;      w += cap * 8 * K;
-    t.box = (uint32_t *) w;  w += cap * 16;
-    t.imin = (uint32_t *) w; w += cap * 4 * K;
-    t.imax = (uint32_t *) w;
-    t.cap = (u64) cap;
-    t.mask = (u64) cap - 1;
-    return t;
-}
-
-u64 *rp_sort_buffer(void *workspace, int64_t cap, int K) { return (u64 *) ((char *) workspace + RP_HEAD_BYTES + cap * rp_row_bytes(K)); }
-
-__device__ __forceinline__ u64 rp_hash(u64 k) {  // splitmix64 finaliser
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
 
 __device__ __noinline__ void rp_global_add(const Table &t, u64 key, const Run &a, int K) {
     u64 h = rp_hash(key) & t.mask;
@@ -386,8 +344,6 @@ __host__ __device__ inline int rp_prop_columns(int code, int K) {
     }
 }
 
-__device__ __forceinline__ int64_t rp_bits(double d) { return (int64_t) __double_as_longlong(d); }
-
 __global__ __launch_bounds__(256) void rp_finalise_kernel(const u64 *__restrict__ sorted, long N, Table t, int K, Props props,
                                                          double sy, double sx, int64_t *__restrict__ out) {
     const long i = (long) blockIdx.x * 256 + threadIdx.x;
@@ -453,8 +409,6 @@ __global__ __launch_bounds__(256) void rp_finalise_kernel(const u64 *__restrict_
     }
     out[(long) col * N + i] = channel;  // one more row after the requested columns
 }
-
-bool rp_bad_capacity(int64_t cap) { return cap < 2 || cap > RP_MAX_CAPACITY || (cap & (cap - 1)); }
 
 int64_t rp_sort_length(int64_t entries) {
     int64_t m = 1024;

@@ -90,7 +90,9 @@ def _resolve(properties):
         canon = ALIASES.get(p, p)
         if canon not in PROP_CODES:
             raise NotImplementedError(f'region_properties: property {p!r} is not implemented on the HIP path; supported: '
-                                      f'{", ".join(SUPPORTED)} (and the old names {", ".join(ALIASES)})')
+                                      f'{", ".join(SUPPORTED)} (and the old names {", ".join(ALIASES)}); perimeter, '
+                                      'perimeter_crofton, euler_number, area_convex and solidity come from shape_properties '
+                                      'and labels2property_table')
         out.append((p, canon))
     if len(out) > MAX_PROPERTIES:
         raise NotImplementedError(f'region_properties: more than {MAX_PROPERTIES} properties')
@@ -123,9 +125,26 @@ def _default_capacity(pixels):
     return cap
 
 
-def _table(labels, properties, intensity_image, spacing, separator, iter_channels, table_capacity):
-    """-> (column names, column kinds, int64 Tensor[columns + 1, rows] on the GPU (last row: channel), intensity dtype, stats)."""
-    props = _resolve(properties)
+def _spacing(spacing):
+    if spacing is None:
+        return 1., 1.
+    if np.isscalar(spacing):
+        return float(spacing), float(spacing)
+    sy, sx = (float(s) for s in spacing)
+    return sy, sx
+
+
+class _Accumulated:
+    """The sorted table of one label image on the device: what the accumulate, status and sort calls leave behind, for the
+    finalisation of this module and the shape pass of ``shape_props``."""
+    __slots__ = ('x', 'H', 'W', 'C', 'K', 'img_dtype', 'ws', 'cap', 'grown', 'rows')
+
+    def stats(self):
+        return dict(table_capacity=self.cap, grown=self.grown, rows=self.rows, channels=self.C)
+
+
+def _accumulate(labels, intensity_image, iter_channels, table_capacity, intensity_requested=False):
+    """Checks the images, uploads them and runs accumulate / table_status / compact_sort -> ``_Accumulated``."""
     x = labels
     _check_integers(x, 'labels')
     if x.ndim == 3 and not iter_channels:
@@ -162,20 +181,10 @@ def _table(labels, properties, intensity_image, spacing, separator, iter_channel
             img = _to_int32(img, 'intensity_image')
         idt = _INTENSITY_DTYPES[img.dtype]
         img = img.contiguous()
-    elif any(canon in _INTENSITY for _, canon in props):
+    elif intensity_requested:
         raise AttributeError('region_properties: an intensity property was requested without an intensity_image')
-    if spacing is None:
-        sy = sx = 1.
-    elif np.isscalar(spacing):
-        sy = sx = float(spacing)
-    else:
-        sy, sx = (float(s) for s in spacing)
-    names, kinds = _column_names(props, separator, K)
     x = _aligned(_to_int32(x, 'labels'))
     lib = _lib.load()
-    codes = (c_int32 * len(props))(*[PROP_CODES[canon] for _, canon in props])
-    ncols = int(lib.cpn_props_columns(codes, len(props), K))
-    assert ncols == len(names), (ncols, names)
     cap = _default_capacity(H * W) if table_capacity is None else int(table_capacity)
     if cap < 2 or cap & (cap - 1):
         raise ValueError('table_capacity must be a power of two')
@@ -193,11 +202,69 @@ def _table(labels, properties, intensity_image, spacing, separator, iter_channel
             cap *= 2
             grown += 1
         n = int(status[1])
-        out = torch.empty((ncols + 1, n), dtype=torch.int64, device=x.device)
         check(lib.cpn_props_compact_sort(ptr(ws), cap, K, n, stream_ptr()), 'props_compact_sort')
-        check(lib.cpn_props_finalise(ptr(ws), cap, K, n, codes, len(props), sy, sx, ptr(out), ncols + 1, stream_ptr()),
-              'props_finalise')
-    return names, kinds, out, img_dtype, dict(table_capacity=cap, grown=grown, rows=n, channels=C)
+    acc = _Accumulated()
+    acc.x, acc.H, acc.W, acc.C, acc.K, acc.img_dtype, acc.ws, acc.cap, acc.grown, acc.rows = x, H, W, C, K, img_dtype, ws, cap, grown, n
+    return acc
+
+
+def _finalise(acc, props, sy, sx):
+    """-> int64 Tensor[columns + 1, rows] on the GPU (last row: channel) for the resolved properties."""
+    lib = _lib.load()
+    codes = (c_int32 * len(props))(*[PROP_CODES[canon] for _, canon in props])
+    ncols = int(lib.cpn_props_columns(codes, len(props), acc.K))
+    with torch.cuda.device(acc.x.device):
+        out = torch.empty((ncols + 1, acc.rows), dtype=torch.int64, device=acc.x.device)
+        check(lib.cpn_props_finalise(ptr(acc.ws), acc.cap, acc.K, acc.rows, codes, len(props), sy, sx, ptr(out), ncols + 1,
+                                     stream_ptr()), 'props_finalise')
+    return out
+
+
+def _table(labels, properties, intensity_image, spacing, separator, iter_channels, table_capacity):
+    """-> (column names, column kinds, int64 Tensor[columns + 1, rows] on the GPU (last row: channel), intensity dtype, stats)."""
+    props = _resolve(properties)
+    acc = _accumulate(labels, intensity_image, iter_channels, table_capacity, any(canon in _INTENSITY for _, canon in props))
+    sy, sx = _spacing(spacing)
+    names, kinds = _column_names(props, separator, acc.K)
+    out = _finalise(acc, props, sy, sx)
+    assert out.shape[0] == len(names) + 1, (out.shape, names)
+    return names, kinds, out, acc.img_dtype, acc.stats()
+
+
+def _mixed_table(labels, properties, intensity_image, spacing, separator, iter_channels, table_capacity):
+    """``_table`` for a property list that names shape properties (``shape_props``) among the others: one accumulate / sort,
+    each engine finalises its own columns, and the rows of both results are put in the order asked for on the device."""
+    from . import shape_props
+    if isinstance(properties, str):
+        properties = (properties,)
+    owners = [shape_props.shape_only(p) for p in properties]
+    rprops = _resolve([p for p, s in zip(properties, owners) if not s])
+    sprops = shape_props._resolve([p for p, s in zip(properties, owners) if s])
+    sy, sx = _spacing(spacing)
+    shape_props._check_spacing(sprops, sy, sx)
+    acc = _accumulate(labels, intensity_image, iter_channels, table_capacity, any(canon in _INTENSITY for _, canon in rprops))
+    parts = []
+    if rprops:
+        parts.append(_finalise(acc, rprops, sy, sx)[:-1])
+    sout, _ = shape_props._finalise(acc, sprops, sy, sx)
+    parts.append(sout)  # its last row is the channel
+    names, kinds, order = [], [], []
+    r_at, s_at = 0, (parts[0].shape[0] if rprops else 0)
+    r_it, s_it = iter(rprops), iter(sprops)
+    for shape in owners:
+        if shape:
+            nm, kd = shape_props._column_names([next(s_it)])
+            at, s_at = s_at, s_at + len(nm)
+        else:
+            nm, kd = _column_names([next(r_it)], separator, acc.K)
+            at, r_at = r_at, r_at + len(nm)
+        names += nm
+        kinds += kd
+        order += list(range(at, at + len(nm)))
+    out = torch.cat(parts)
+    order.append(out.shape[0] - 1)
+    out = out[torch.tensor(order, dtype=torch.int64, device=out.device)]
+    return names, kinds, out, acc.img_dtype, acc.stats()
 
 
 def region_properties(labels, properties=('label', 'bbox'), intensity_image=None, spacing=None, separator='-', iter_channels=True,
@@ -234,6 +301,8 @@ def labels2property_table(labels, *properties, iter_channels=True, **kwargs):
     ``pandas.DataFrame`` with one row per object and one column per property component, built from ONE device-to-host copy.
 
     *properties: property names, or a single list / tuple of them (default: ``('label', 'bbox')`` as ``regionprops_table``).
+    The names of ``shape_props.SUPPORTED`` (``perimeter``, ``perimeter_crofton``, ``euler_number``, ``area_convex``,
+    ``solidity``; ``convex_area``) may be mixed with those of ``SUPPORTED``: the image is accumulated and sorted once.
     **kwargs: ``intensity_image``, ``spacing``, ``separator`` as ``region_properties``; ``df_kwargs``: keyword arguments of
     every per-channel ``pandas.DataFrame``; ``table_capacity``.  The index is the one the reference's per-channel ``pd.concat``
     produces: it restarts at 0 in every channel."""
@@ -254,8 +323,13 @@ def labels2property_table(labels, *properties, iter_channels=True, **kwargs):
     if unknown:
         raise TypeError(f'labels2property_table: unexpected keyword arguments {sorted(unknown)}')
     sep = kwargs.get('separator', '-')
-    names, kinds, out, img_dtype, stats = _table(labels, properties, kwargs.get('intensity_image'), kwargs.get('spacing'), sep,
-                                                   iter_channels, kwargs.get('table_capacity'))
+    from . import shape_props
+    if any(shape_props.shape_only(p) for p in properties):
+        names, kinds, out, img_dtype, stats = _mixed_table(labels, properties, kwargs.get('intensity_image'), kwargs.get('spacing'),
+                                                             sep, iter_channels, kwargs.get('table_capacity'))
+    else:
+        names, kinds, out, img_dtype, stats = _table(labels, properties, kwargs.get('intensity_image'), kwargs.get('spacing'), sep,
+                                                       iter_channels, kwargs.get('table_capacity'))
     host = out.cpu().numpy()  # the one copy
     channel = host[-1]
     np_dtype = None if img_dtype is None else torch.empty(0, dtype=img_dtype).numpy().dtype

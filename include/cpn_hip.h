@@ -610,6 +610,70 @@ int cpn_props_finalise(void *workspace, int64_t table_capacity, int32_t intensit
                        int64_t out_columns, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
+ * Shape property tables of label images: perimeter, perimeter_crofton, euler_number, area_convex, solidity (the outline
+ * properties of skimage.measure.regionprops_table, which cd.data.labels2property_table hands on; csrc/shape_props.hip,
+ * csrc/hull_count.h).  Entry points added to ABI 22 (nothing that existed changed; a library without them fails to load by its
+ * missing symbols).  scikit-image is third-party and not available to this project: the arithmetic is restated
+ * here, and these definitions are the contract.
+ * The calls run after cpn_props_accumulate / table_status / compact_sort on the same label image: props_workspace is that
+ * workspace (read only here: keys, pixel counts, bounding boxes, sorted order), with its table_capacity, intensity_channels
+ * and entries.  Rows are the rows of cpn_props_finalise.  All accumulation is integer arithmetic: bit-identical from run to
+ * run.
+ *   workspace_bytes:    the shape workspace for a table of `table_capacity` slots (0: bad capacity).
+ *   columns:            number of columns of the property list (every property is one column; -1: bad list; host only).
+ *   heights:            heights int64 [entries] on the device: the bounding-box height of every row's object.  Asynchronous.
+ *   accumulate:         zeroes the shape workspace and reads the label image once: per object the three perimeter classes,
+ *                       the four transition counts and the bit-quad sum.  With row_begin != NULL (int64 [entries + 1] on the
+ *                       device: the exclusive scan of `heights`, total_rows at the end; the caller scans) also the column
+ *                       extent of every row of every object into extents (uint32 [2][total_rows], zeroed here).  Asynchronous.
+ *   hull_scratch_bytes: scratch of `hull` (host only).
+ *   hull:               counts int64 [entries] on the device: the lattice points of every object's convex hull, one lane per
+ *                       object (an object as tall as the image serialises).  Asynchronous.
+ *   finalise:           out: int64 [out_columns][entries] as cpn_props_finalise writes it (float columns as fp64 bit patterns,
+ *                       a last row with the channel).  hull_counts may be NULL without area_convex / solidity.  Asynchronous.
+ * Definitions.  For one row (channel z, label l) let M(r, c) = [labels[r][c][z] == l], and 0 outside the image: the predicate
+ * is SAME LABEL, not foreground; a neighbouring pixel of another label counts as outside (as cropping to the bounding box,
+ * regionprops(...).image, does).  n = number of pixels.  (sy, sx) = (spacing_row, spacing_col); s = sy, and perimeter /
+ * perimeter_crofton with sy != sx are CPN_E_UNSUPPORTED (isotropic spacings only, as in scikit-image).  Every float
+ * expression is evaluated in fp64 as written, without contraction; sqrt(2.0) and pi are the fp64 values.
+ *   perimeter (perimeter(image, 4)): B(p) = M(p) and at least one of p's four edge neighbours has M = 0.  For each p with
+ *     B(p): o = the number of its 4 edge neighbours with B, d = the number of its 4 diagonal neighbours with B, code =
+ *     1 + 2 o + 10 d.  n1 = #{code in 5, 7, 15, 17, 25, 27}, n2 = #{code in 21, 33}, n3 = #{code in 13, 23}; every other
+ *     code adds nothing.  perimeter = ((double) n1 + (double) n2 * sqrt(2.0) + (double) n3 * ((1.0 + sqrt(2.0)) / 2.0)) * s.
+ *   perimeter_crofton (perimeter_crofton(image, 4)), as one-sided transition counts: Nv = #{M(r, c) and not M(r - 1, c)},
+ *     Nh = #{M(r, c) and not M(r, c + 1)}, Nd = #{M(r, c) and not M(r - 1, c - 1)}, Na = #{M(r, c) and not M(r + 1, c - 1)};
+ *     perimeter_crofton = (((double) (Nv + Nh) + (double) (Nd + Na) / sqrt(2.0)) * (pi / 4.0)) * s.
+ *   euler_number (int64, ignores the spacing): 8-connected components of M minus 4-connected holes = (Q1 - Q3 - 2 QD) / 4 over
+ *     all 2 x 2 windows of the zero-padded mask, (H + 1) x (W + 1) positions: Q1 / Q3 windows with one / three set pixels,
+ *     QD windows with exactly the two diagonal pixels set.
+ *   area_convex, solidity (convex_hull_image with offset_coordinates=True, include_borders=True): K = the closed convex hull
+ *     of the points (r +- 1/2, c) and (r, c +- 1/2) over all pixels of M; cnt = the number of integer points (r, c) in K,
+ *     decided with 64-bit integer cross products in doubled coordinates; area_convex = (double) cnt * (sy * sx);
+ *     solidity = ((double) n * (sy * sx)) / area_convex.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_SHAPE_LABEL 0
+#define CPN_SHAPE_NUM_PIXELS 1
+#define CPN_SHAPE_PERIMETER 2
+#define CPN_SHAPE_PERIMETER_CROFTON 3
+#define CPN_SHAPE_EULER_NUMBER 4
+#define CPN_SHAPE_AREA_CONVEX 5
+#define CPN_SHAPE_SOLIDITY 6
+#define CPN_SHAPE_COUNT 7
+int64_t cpn_shape_workspace_bytes(int64_t table_capacity);
+int32_t cpn_shape_columns(const int32_t *properties, int32_t n_properties);
+int cpn_shape_heights(void *props_workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, int64_t *heights,
+                      void *stream);
+int cpn_shape_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t channels, void *props_workspace, int64_t table_capacity,
+                         int32_t intensity_channels, int64_t entries, void *workspace, int64_t workspace_bytes,
+                         const int64_t *row_begin, uint32_t *extents, int64_t total_rows, void *stream);
+int64_t cpn_shape_hull_scratch_bytes(int64_t entries, int64_t total_rows);
+int cpn_shape_hull(int64_t entries, const int64_t *row_begin, const uint32_t *extents, int64_t total_rows, void *scratch,
+                   int64_t scratch_bytes, int64_t *counts, void *stream);
+int cpn_shape_finalise(void *props_workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, void *workspace,
+                       const int64_t *hull_counts, const int32_t *properties, int32_t n_properties, double spacing_row,
+                       double spacing_col, int64_t *out, int64_t out_columns, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
  * Overlay images (cd.data.contours2overlay, celldetection/data/cpn.py:647-662,699-723,811-855, and cd.label_cmap(ubyte=True),
  * celldetection/visualization/cmaps.py:21-77; both called from celldetection_scripts/cpn_inference.py:839-848;
  * csrc/overlay.hip).  ABI 19.  out: uint8 [H][W][4] (r, g, b, a) on the device, 4-byte aligned.  H * W <= 2^31 - 1
