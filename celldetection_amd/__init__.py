@@ -6,12 +6,13 @@ loop.  Everything computes in hand-written HIP kernels behind the C ABI of ``lib
 (``include/cpn_hip.h``); there is no CPU fallback.
 """
 from . import cpn as models  # ``cd.models.CpnResNeXt101UNet`` -> ``celldetection_amd.models.CpnResNeXt101UNet``
-from . import (flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, ops, overlay, preprocess, region_props, shape_props, synth,
+from . import (flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, objective, ops, overlay, preprocess, region_props, shape_props, synth,
                targets, util)
 from .flat_labels import resolve_label_channels
 from .fourier import contours2fourier, efd, labels2fourier
 from .h5 import from_h5, to_h5
 from .instance_eval import LabelMatcher, LabelMatcherList
+from .objective import CPNObjective, collate_cpn_targets
 from .region_props import labels2property_table, region_properties
 from .shape_props import shape_properties
 from .label_contours import labels2contour_list as labels2contours  # ``cd.data.labels2contours`` is that function
@@ -26,4 +27,5 @@ __all__ = ['models', 'ops', 'util', 'synth', 'inference', 'labels', 'contours2la
            'model2dict', 'get_tiling_slices', 'instance_eval', 'LabelMatcher', 'LabelMatcherList', 'flat_labels',
            'resolve_label_channels', 'region_props', 'region_properties', 'labels2property_table', 'shape_props', 'shape_properties', 'overlay', 'contours2overlay',
            'label_cmap', 'random_colors_hsv', 'label_contours', 'labels2contours', 'resample_contours', 'fourier', 'efd', 'contours2fourier',
-           'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator']
+           'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator',
+           'objective', 'CPNObjective', 'collate_cpn_targets']

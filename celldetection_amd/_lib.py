@@ -33,6 +33,9 @@ PROPS_U8, PROPS_I16, PROPS_I32 = 0, 1, 2
 # shape properties (CPN_SHAPE_* of include/cpn_hip.h), in code order
 SHAPE_NAMES = ('label', 'num_pixels', 'perimeter', 'perimeter_crofton', 'euler_number', 'area_convex', 'solidity')
 SHAPE_CODES = {name: code for code, name in enumerate(SHAPE_NAMES)}
+# training objective (CPN_OBJECTIVE_* of include/cpn_hip.h)
+OBJECTIVE_MAX_ITERATIONS, OBJECTIVE_META_WORDS = 64, 2
+OBJECTIVE_FLAG_LABEL_RANGE, OBJECTIVE_FLAG_LABEL_ROWS, OBJECTIVE_FLAG_CLASS_RANGE = 1, 2, 4
 
 
 class TensorDesc(Structure):
@@ -49,6 +52,18 @@ class OpDesc(Structure):
                 ('dst_coff', c_int32), ('in_channels', c_int32),
                 ('fuse_weight_offset', c_int64), ('fuse_bias_offset', c_int64), ('fuse_cout', c_int32),
                 ('fuse_act', c_int32), ('fuse_act_scale', c_float), ('mult_offset', c_int32), ('subpixel', c_int32), ('alt', c_int32)]
+
+
+class ObjectiveArgs(Structure):
+    """CpnObjectiveArgs of include/cpn_hip.h (section "Training objective")."""
+    _fields_ = [(n, c_void_p) for n in ('scores', 'locations', 'refinement', 'fourier', 'labels', 't_fourier', 't_locations',
+                                        't_contours', 't_classes', 'cos_table', 'sin_table', 'bucket_index', 'bucket_weight',
+                                        'order_weights', 'g_scores', 'g_locations', 'g_refinement', 'g_fourier',
+                                        'detail_proposals', 'detail_refined', 'detail_boxes')] + \
+               [(n, c_double) for n in ('w_fourier', 'w_location', 'w_contour', 'w_score_fg', 'w_score_bg', 'w_refinement',
+                                        'w_iou')] + \
+               [(n, c_int32) for n in ('N', 'score_channels', 'h', 'w', 'H', 'W', 'order_total', 'order', 'samples', 'K',
+                                       'iterations', 'buckets', 'labels_i64', 'reserved')]
 
 
 # every symbol include/cpn_hip.h declares: (name, restype, argtypes)
@@ -206,6 +221,11 @@ _SIGNATURES = [
                                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     ('cpn_label_distances_mask', ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     ('cpn_label_remap', ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    ('cpn_objective_head_workspace_bytes', c_int64, [c_int32, c_int32, c_int32]),
+    ('cpn_objective_head', ctypes.c_int, [POINTER(ObjectiveArgs), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    ('cpn_objective_workspace_bytes', c_int64, [POINTER(ObjectiveArgs), c_int64]),
+    ('cpn_objective_proposals', ctypes.c_int, [POINTER(ObjectiveArgs), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                               c_int64, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

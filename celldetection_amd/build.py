@@ -43,6 +43,9 @@ SOURCES = {
     'contour_fourier.hip': ['-ffp-contract=off'],
     # integer chamfer relaxation; the float32 normalisation is one IEEE division per pixel: correctly rounded, no contraction
     'label_distances.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+    # the training objective shares the decode's float32 arithmetic (decode_device.h) and defines its float64 sums and gradients
+    # by their order of operations: no FMA contraction
+    'cpn_objective.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -51,7 +54,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'props_table.h', 'hull_count.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -8,6 +8,8 @@ operator the reference calls directly (celldetection/ops/cpn.py:181,211,216,223;
 426; celldetection/models/lightning_cpn.py:167): with it those call sites run on the HIP NMS without being edited.
 """
 import torch
+from typing import Optional
+
 from torch import Tensor
 
 from . import ops as _ops
@@ -15,7 +17,7 @@ from . import ops as _ops
 __all__ = ['install_torchvision_nms', 'NAMESPACE']
 
 NAMESPACE = 'cpn_hip'
-OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap / .labels2contours_packed / .resample_contours / .labels2distances
+OVERLAY_NAMESPACE = 'celldetection_amd'  # torch.ops.celldetection_amd.contours2overlay / .label_cmap / .labels2contours_packed / .resample_contours / .labels2distances / .cpn_objective
 _lib_keepalive = []
 
 
@@ -193,6 +195,32 @@ def labels2distances(labels: Tensor, distance_type: int, per_instance: bool, pro
 def _(labels, distance_type, per_instance, protected_size):
     return (labels.new_empty(tuple(labels.shape[:2]), dtype=torch.float32),
             labels.new_empty(tuple(labels.shape[:2]) + (labels.shape[2] if labels.ndim == 3 else 1,)))
+
+
+@torch.library.custom_op(f'{OVERLAY_NAMESPACE}::cpn_objective', mutates_args=(), device_types='cuda')
+def cpn_objective(scores: Tensor, locations: Tensor, refinement: Optional[Tensor], fourier: Tensor, labels: Tensor,
+                  target_fourier: Tensor, target_locations: Tensor, target_contours: Tensor, sampling: Tensor, height: int, width: int,
+                  classes: int, refinement_iterations: int, refinement_buckets: int,
+                  order_weights: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """CPN training objective (celldetection/models/cpn.py:441-692) with the reference's default weights: the four head maps and
+    the batch targets -> float32 [9] (the eight terms in the reference's order, NaN where a term does not apply, then the loss)
+    and the gradients of the loss by scores, locations, fourier and refinement (an empty tensor without a refinement map); see
+    ``objective.CPNObjective``, which is the differentiable form."""
+    from . import objective
+    obj = objective.CPNObjective(int(target_fourier.shape[2]), int(sampling.shape[1]), classes=classes, refinement=refinement is not None,
+                                 refinement_iterations=refinement_iterations, refinement_buckets=refinement_buckets,
+                                 order_weights=order_weights)
+    targets = dict(labels=labels, fourier=target_fourier, locations=target_locations, sampled_contours=target_contours,
+                   sampling=sampling)
+    out, _, grads, _ = objective._run(obj, scores, locations, refinement, fourier, targets, (height, width), [True] * 4, False)
+    return out, grads[0], grads[1], grads[3], grads[2] if grads[2] is not None else scores.new_empty((0,))
+
+
+@cpn_objective.register_fake
+def _(scores, locations, refinement, fourier, labels, target_fourier, target_locations, target_contours, sampling, height, width,
+      classes, refinement_iterations, refinement_buckets, order_weights):
+    return (scores.new_empty((9,)), torch.empty_like(scores), torch.empty_like(locations), torch.empty_like(fourier),
+            torch.empty_like(refinement) if refinement is not None and refinement_iterations > 0 else scores.new_empty((0,)))
 
 
 def install_torchvision_nms(force: bool = False) -> bool:

@@ -855,6 +855,85 @@ int cpn_label_distances_mask(int32_t *labels, int32_t channels, int64_t pixels, 
                              float min_fg_dist, int32_t *reduced, void *stream);
 int cpn_label_remap(int32_t *labels, int64_t elements, const int32_t *keys, const int32_t *values, int32_t entries, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Training objective (the reference's CPN.forward(inputs, targets) in training mode, celldetection/models/cpn.py:561-692 with
+ * compute_loss :441-559; csrc/cpn_objective.hip).  Additions to ABI 22.  This text is the contract.
+ *
+ * Inputs, all on the device.  Head maps, float32 NCHW: scores [N][score_channels][h][w] raw logits (1 channel: binary,
+ * otherwise one per class), locations [N][2][h][w] relative (x, y), fourier [N][4 * order_total][h][w] of which the first
+ * `order` coefficient rows are used, refinement [N][2 * buckets][H][W] or NULL.  Targets: labels [N][H][W] (int32, or int64 with
+ * labels_i64 != 0), t_fourier [N][K][order][4], t_locations [N][K][2], t_contours [N][K][samples][2], t_classes int32 [N][K] or
+ * NULL; cos_table / sin_table float32 [N][order][samples] of every image's own sampling (ops/cpn.py:66-78) and, with buckets > 1,
+ * bucket_index int32 / bucket_weight float32 [N][3][samples] (ops/cpn.py:238-255), all four built by the caller with the
+ * reference's expressions; order_weights float32 [order] or NULL (= 1).
+ *
+ * The rule.
+ *  Labels go to the head grid by max pooling with kernel (H / h, W / w) (integer division, no padding) and, when the pooled
+ *  size still differs from (h, w), by nearest interpolation (source index floor(i * float(in) / float(out)), at most in - 1).
+ *  Foreground is > 0, background == 0; negative pixels are in neither set.
+ *  Proposals are all foreground head pixels in (b, y, x) row-major order; proposal p takes the target row `label - 1` of its
+ *  image b.  Its contour is decoded in float32 with the tables of image b exactly as cpn_decode does: ((location + pixel
+ *  position) + sum of the sin terms) + sum of the cos terms, then times (float(W) / float(w), float(H) / float(h)); the
+ *  selected coefficients and the absolute location are scaled after the decode.
+ *  Refinement, `iterations` times: round half to even, clamp to the image, gather (three weighted buckets when buckets > 1),
+ *  add -- as cpn_local_refinement.  Every refined set is clamped to [0, W - 1] x [0, H - 1] before it is used; without a
+ *  refinement map or with iterations == 0 it is the proposals that are clamped.  A clamp passes a gradient where the value
+ *  lay inside the closed range; nothing passes through the rounding.
+ *  Box = minimum and maximum over the samples of the last set; on equal values the gradient goes to the lowest sample.
+ *  Terms (n = number of elements; every |a - b| is a float32 difference, every sum float64 in an order fixed by the shapes):
+ *   fourier    w_fourier * mean(|f * scale - t_fourier| * order_weights),         n = P * order * 4
+ *   location   w_location * mean(|loc * scale - t_locations|),                    n = P * 2
+ *   contour    w_contour * mean(|proposals - t_contours|),                        n = P * samples * 2
+ *   refinement sum over the iterations of w_refinement * mean(|set - t_contours|)
+ *   score      score_channels == 1: w_score_fg * mean over the foreground of BCE-with-logits(z, 1) + w_score_bg * mean over the
+ *              background of BCE-with-logits(z, 0); otherwise cross entropy against t_classes[b][label - 1] (or 1) and 0.  A
+ *              part whose set is empty is left out.  Elements are float64 functions of the float32 logits.
+ *   iou        w_iou * mean of 1 - GIoU(box, target box) over the proposals whose box has float32 width and height >= 1; the
+ *              target box is the minimum and maximum of the target contour; float64; no such proposal: 0.
+ *  A mean that is not finite as float32 counts as 0 (add_to_loss_dict).  Every term is rounded to float32 once; the loss is
+ *  the float32 sum of the terms that apply, in the order fourier, location, contour, score, refinement, boxes, iou, uncertainty.
+ *  Gradients are the analytic derivatives of that loss in float64, rounded to float32 once per element (sign(0) = 0; equal
+ *  arguments of a maximum or minimum of two boxes share the gradient evenly; clamp(min = 0) passes it on >= 0).
+ *
+ * The calls.
+ *  cpn_objective_head (asynchronous): label pooling, foreground compaction (cpn_compact), the score elements and g_scores.
+ *   indices: int32 [N * h * w], receives the proposals' head pixels b * h * w + y * w + x.  meta: int32 [N + 1 +
+ *   CPN_OBJECTIVE_META_WORDS]: proposals per image, P at [N], then the number of background pixels and the CPN_OBJECTIVE_FLAG_*
+ *   bits.  The caller reads meta (its one synchronisation), refuses set flags, sizes the second workspace by P.
+ *  cpn_objective_proposals (asynchronous): the proposal walks, the reduction and the remaining gradients.  `present`: bit k set:
+ *   term k (order above) applies.  out: float32 [9] on the device: the eight terms (NaN where not present) and the loss.
+ *   g_scores / g_locations / g_fourier / g_refinement: NULL or a buffer of the map's shape; every element is written.
+ *   detail_proposals [P][samples][2], detail_refined [iterations][P][samples][2] (clamped), detail_boxes [P][4]: NULL or buffers.
+ *  The gradient of the refinement map is the one scatter: one contribution per (proposal, iteration, sample, bucket), sorted by
+ *  element with a stable radix sort and summed in float64 in an order that depends on the sorted list alone.  No floating-point atomics: all results are
+ *  bit-identical from run to run.  P * samples * iterations * (buckets > 1 ? 3 : 1) and N * buckets * H * W stay below 2^32.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_OBJECTIVE_MAX_ITERATIONS 64
+#define CPN_OBJECTIVE_META_WORDS 2
+#define CPN_OBJECTIVE_FLAG_LABEL_RANGE 1 /* a pooled label above 2^24 (the reference moves labels through float32) */
+#define CPN_OBJECTIVE_FLAG_LABEL_ROWS 2  /* a pooled label above K */
+#define CPN_OBJECTIVE_FLAG_CLASS_RANGE 4 /* a class target outside 0 .. score_channels - 1 */
+typedef struct CpnObjectiveArgs {
+    const float *scores, *locations, *refinement, *fourier;
+    const void *labels;
+    const float *t_fourier, *t_locations, *t_contours;
+    const int32_t *t_classes;
+    const float *cos_table, *sin_table;
+    const int32_t *bucket_index;
+    const float *bucket_weight;
+    const float *order_weights;
+    float *g_scores, *g_locations, *g_refinement, *g_fourier;
+    float *detail_proposals, *detail_refined, *detail_boxes;
+    double w_fourier, w_location, w_contour, w_score_fg, w_score_bg, w_refinement, w_iou;
+    int32_t N, score_channels, h, w, H, W, order_total, order, samples, K, iterations, buckets, labels_i64, reserved;
+} CpnObjectiveArgs;
+int64_t cpn_objective_head_workspace_bytes(int32_t N, int32_t h, int32_t w);
+int cpn_objective_head(const CpnObjectiveArgs *args, int32_t *indices, int32_t *meta, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+int64_t cpn_objective_workspace_bytes(const CpnObjectiveArgs *args, int64_t P);
+int cpn_objective_proposals(const CpnObjectiveArgs *args, const int32_t *indices, int32_t P, const int32_t *meta, int32_t present,
+                            void *head_workspace, void *workspace, int64_t workspace_bytes, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
