@@ -6,7 +6,7 @@
 //   * one count per ELEMENT > 0 to the area of that label (a value in two channels of a pixel counts twice, like
 //     np.unique(..., return_counts=True) over the whole array), and
 //   * one count per DISTINCT pair (input label > 0, target label > 0) at that pixel.
-// All three kinds of counter live in ONE open-addressing hash table in global memory on a 64-bit key:
+// All three kinds of counter live in ONE open-addressing hash table (csrc/label_table.h) in global memory on a 64-bit key:
 //   input area  (l << 32) | 0      target area  (0 << 32) | l      pair  (input << 32) | target
 // (labels are > 0, so the three ranges cannot collide and key 0 means "empty").  A slot is claimed with a 64-bit
 // compare-and-swap and counted with 64-bit integer adds: order-independent, hence reproducible run to run.
@@ -29,44 +29,26 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "label_table.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int EV_MAX_C = 8;          // channels supported per side
 constexpr int EV_VEC_C = 4;          // up to this many channels per side: kernels for the exact channel counts
 constexpr int EV_VEC_SLOTS = 15;     // up to this many slots (CA + CB + CA * CB): vector loads + register run-lengths
 constexpr int EV_PPT = 8;            // consecutive pixels per thread in the vector kernels
-constexpr u64 EV_MAX_PROBE = 4096;   // probes before an insert reports overflow
+constexpr int64_t EV_MAX_CAPACITY = (int64_t) 1 << 40;
 
 struct Table {
     u64 *keys, *counts;
-    u64 mask;       // capacity - 1 (capacity is a power of two)
+    u64 cap;        // a power of two
     u64 *overflow;  // inserts that found no slot
 };
 
-__device__ __forceinline__ u64 ev_hash(u64 k) {  // splitmix64 finaliser
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
 __device__ __noinline__ void ev_insert(const Table t, u64 key, u64 n) {
-    u64 h = ev_hash(key) & t.mask;
-    const u64 limit = t.mask + 1 < EV_MAX_PROBE ? t.mask + 1 : EV_MAX_PROBE;
-    for (u64 i = 0; i < limit; ++i, h = (h + 1) & t.mask) {
-        u64 cur = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0) {
-            cur = atomicCAS(&t.keys[h], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur == key) {
-            atomicAdd(&t.counts[h], n);
-            return;
-        }
-    }
-    atomicAdd(t.overflow, 1ull);
+    const i64 h = lt_claim(t.keys, t.cap, key);
+    if (h >= 0) atomicAdd(&t.counts[h], n);
+    else atomicAdd(t.overflow, 1ull);
 }
 
 // All 64 lanes call this together.  Lanes hold (key, n); runs of equal keys in consecutive lanes are summed into the
@@ -76,14 +58,7 @@ __device__ __forceinline__ void ev_wave_flush(const Table &t, u64 key, unsigned 
     const int lane = __lane_id();
     const u64 prev = __shfl_up(key, 1, 64);
     const bool head = lane == 0 || prev != key;
-    const u64 heads = __ballot(head);
-    const int run = __popcll(heads & (~0ull >> (63 - lane)));
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned on = __shfl_down(n, d, 64);
-        const int orun = __shfl_down(run, d, 64);
-        if (lane + d < 64 && orun == run) n += on;
-    }
+    n = lt_segment_sum(head, n);
     if (head && key != 0 && n != 0) ev_insert(t, key, n);
 }
 
@@ -168,33 +143,14 @@ __global__ __launch_bounds__(256) void ev_pixel_kernel(const int32_t *__restrict
 }
 
 // table -> compact arrays --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ev_count_kernel(const u64 *__restrict__ keys, long cap, u64 *__restrict__ entries) {
-    unsigned n = 0;
-    for (long i = (long) blockIdx.x * 256 + threadIdx.x; i < cap; i += (long) gridDim.x * 256) n += keys[i] != 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(entries, (u64) n);
-}
-
-__global__ __launch_bounds__(256) void ev_compact_kernel(const u64 *__restrict__ keys, const u64 *__restrict__ counts, long cap,
-                                                        u64 *__restrict__ cursor, int64_t *__restrict__ keys_out,
-                                                        int64_t *__restrict__ counts_out, long n_out) {
-    const int lane = threadIdx.x & 63;
-    const long rounds = (cap + (long) gridDim.x * 256 - 1) / ((long) gridDim.x * 256);  // uniform trip count: ballots inside
-    for (long r = 0; r < rounds; ++r) {
-        const long i = (r * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        const u64 k = i < cap ? keys[i] : 0;
-        const u64 m = __ballot(k != 0);
-        if (m == 0) continue;
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(cursor, (u64) __popcll(m));
-        base = __shfl(base, 0, 64);
-        if (k != 0) {
-            const long pos = (long) base + __popcll(m & ((1ull << lane) - 1));
-            if (pos < n_out) { keys_out[pos] = (int64_t) k; counts_out[pos] = (int64_t) counts[i]; }
-        }
+struct KeyCountEmit {  // what lt_compact_kernel writes per occupied slot
+    const u64 *__restrict__ counts;
+    int64_t *__restrict__ keys_out, *__restrict__ counts_out;
+    __device__ void operator()(long pos, long slot, u64 k) const {
+        keys_out[pos] = (int64_t) k;
+        counts_out[pos] = (int64_t) counts[slot];
     }
-}
+};
 
 // pairs -> label positions and unions ---------------------------------------------------------------------------------
 __device__ __forceinline__ int ev_find(const int64_t *__restrict__ v, int n, int64_t x) {  // position of x in sorted v, or -1
@@ -298,8 +254,6 @@ __global__ __launch_bounds__(256) void ev_sel_prune_kernel(Sel s) {
     }
 }
 
-constexpr int64_t EV_HEAD_BYTES = 64;  // counters in front of the workspace: [0] overflow, [1] entries, [2] cursor, [3] missing
-
 inline int64_t ev_align(int64_t n) { return (n + 63) & ~(int64_t) 63; }
 
 // Register run-lengths pay while a thread's slots are few: measured on 16384^2 images of 10^5 objects, 2 x 2 channels
@@ -332,13 +286,12 @@ extern "C" {
 int64_t cpn_eval_workspace_bytes(int64_t table_capacity, int64_t pairs, int64_t labels) {
     if (table_capacity < 0 || pairs < 0 || labels < 0) return 0;
     // table: keys + counts; selection: alive + sel-side flags per pair, best (int32) + taken (u8) per label and side
-    return EV_HEAD_BYTES + table_capacity * 16 + ev_align(pairs) + 2 * ev_align(labels * 4) + 2 * ev_align(labels);
+    return LT_HEAD_BYTES + table_capacity * 16 + ev_align(pairs) + 2 * ev_align(labels * 4) + 2 * ev_align(labels);
 }
 
 int cpn_eval_pairs(const int32_t *inputs, int32_t c_in, const int32_t *targets, int32_t c_t, int64_t pixels,
                    int64_t table_capacity, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (c_in < 1 || c_t < 1 || pixels < 0 || table_capacity < 2 || table_capacity > ((int64_t) 1 << 40) ||
-        (table_capacity & (table_capacity - 1)) || !workspace)
+    if (c_in < 1 || c_t < 1 || pixels < 0 || lt_bad_capacity(table_capacity, EV_MAX_CAPACITY) || !workspace)
         return cpn::fail(CPN_E_INVALID, "cpn_eval_pairs: bad arguments (table_capacity must be a power of two)");
     if (c_in > EV_MAX_C || c_t > EV_MAX_C)
         return cpn::fail(CPN_E_UNSUPPORTED, "cpn_eval_pairs: more than 8 channels per label image");
@@ -347,11 +300,11 @@ int cpn_eval_pairs(const int32_t *inputs, int32_t c_in, const int32_t *targets, 
     if (workspace_bytes < cpn_eval_workspace_bytes(table_capacity, 0, 0))
         return cpn::fail(CPN_E_WORKSPACE, "cpn_eval_pairs: workspace too small");
     hipStream_t st = (hipStream_t) stream;
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t) (EV_HEAD_BYTES + table_capacity * 16), st);
+    hipError_t e = hipMemsetAsync(workspace, 0, (size_t) (LT_HEAD_BYTES + table_capacity * 16), st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_eval_pairs: memset");
     if (pixels == 0) return 0;
     u64 *head = (u64 *) workspace;
-    Table t{head + EV_HEAD_BYTES / 8, head + EV_HEAD_BYTES / 8 + table_capacity, (u64) table_capacity - 1, head};
+    Table t{lt_keys(workspace), lt_keys(workspace) + table_capacity, (u64) table_capacity, head};
     if (pixels > (int64_t) 0x7fffffff * 256) return cpn::fail(CPN_E_UNSUPPORTED, "cpn_eval_pairs: image too large");
     if (c_in <= EV_VEC_C && c_t <= EV_VEC_C) {
         switch (c_in) {
@@ -368,16 +321,9 @@ int cpn_eval_pairs(const int32_t *inputs, int32_t c_in, const int32_t *targets, 
 }
 
 int cpn_eval_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream) {
-    if (!workspace || !status_host || table_capacity < 2) return cpn::fail(CPN_E_INVALID, "cpn_eval_table_status: bad arguments");
-    hipStream_t st = (hipStream_t) stream;
-    u64 *head = (u64 *) workspace;
-    const unsigned blocks = (unsigned) ((table_capacity + 255) / 256 < 4096 ? (table_capacity + 255) / 256 : 4096);
-    hipLaunchKernelGGL(ev_count_kernel, dim3(blocks), dim3(256), 0, st, head + EV_HEAD_BYTES / 8, (long) table_capacity,
-                       head + 1);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(status_host, head, 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return cpn::check_hip(e, "cpn_eval_table_status");
+    if (!workspace || !status_host || lt_bad_capacity(table_capacity, EV_MAX_CAPACITY))
+        return cpn::fail(CPN_E_INVALID, "cpn_eval_table_status: bad arguments");
+    return cpn::check_hip(lt_status(workspace, table_capacity, status_host, (hipStream_t) stream), "cpn_eval_table_status");
 }
 
 int cpn_eval_compact(void *workspace, int64_t table_capacity, int64_t *keys, int64_t *counts, int64_t entries, void *stream) {
@@ -388,9 +334,9 @@ int cpn_eval_compact(void *workspace, int64_t table_capacity, int64_t *keys, int
     u64 *head = (u64 *) workspace;
     hipError_t e = hipMemsetAsync(head + 2, 0, 8, st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_eval_compact: memset");
-    const unsigned blocks = (unsigned) ((table_capacity + 255) / 256 < 4096 ? (table_capacity + 255) / 256 : 4096);
-    hipLaunchKernelGGL(ev_compact_kernel, dim3(blocks), dim3(256), 0, st, head + EV_HEAD_BYTES / 8,
-                       head + EV_HEAD_BYTES / 8 + table_capacity, (long) table_capacity, head + 2, keys, counts, (long) entries);
+    hipLaunchKernelGGL(lt_compact_kernel<KeyCountEmit>, dim3(lt_scan_blocks(table_capacity)), dim3(256), 0, st, lt_keys(workspace),
+                       (long) table_capacity, head + 2, KeyCountEmit{lt_keys(workspace) + table_capacity, keys, counts},
+                       (long) entries);
     return cpn::check_hip(hipGetLastError(), "cpn_eval_compact");
 }
 
@@ -434,13 +380,13 @@ int cpn_eval_select(const int64_t *intersections, const int64_t *unions, const i
     s.inter = intersections; s.unions = unions; s.in_idx = input_index; s.t_idx = target_index; s.P = (long) pairs;
     s.sel = selected;
     s.counters = (u64 *) w;
-    w += EV_HEAD_BYTES;
+    w += LT_HEAD_BYTES;
     s.alive = (uint8_t *) w;     w += ev_align(pairs);
     s.best_in = (int32_t *) w;   w += ev_align(labels * 4);
     s.best_t = (int32_t *) w;    w += ev_align(labels * 4);
     s.taken_in = (uint8_t *) w;  w += ev_align(labels);
     s.taken_t = (uint8_t *) w;
-    hipError_t e = hipMemsetAsync(s.counters, 0, EV_HEAD_BYTES, st);
+    hipError_t e = hipMemsetAsync(s.counters, 0, LT_HEAD_BYTES, st);
     if (e == hipSuccess) e = hipMemsetAsync(s.best_in, 0xff, (size_t) (2 * ev_align(labels * 4)), st);
     if (e == hipSuccess) e = hipMemsetAsync(s.taken_in, 0, (size_t) (2 * ev_align(labels)), st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_eval_select: memset");

@@ -1,18 +1,16 @@
-// Layout of the region property workspace (csrc/region_props.hip writes it, csrc/shape_props.hip reads it): counters, the
-// open-addressing table keyed by (channel << 32 | label) and the sort buffer of (channel << 59 | label << 28 | slot).
+// Layout of the region property workspace (csrc/region_props.hip writes it, csrc/shape_props.hip reads it): the counters and
+// the table of csrc/label_table.h keyed by (channel << 32 | label), its rows, and the sort buffer of
+// (channel << 59 | label << 28 | slot).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
+#include "label_table.h"
+
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
 constexpr int RP_MAX_K = 4;          // intensity channels
-constexpr u64 RP_MAX_PROBE = 4096;   // probes before an insert reports overflow
-constexpr int64_t RP_HEAD_BYTES = 64;  // counters in front of the workspace: [0] overflow, [1] entries, [2] cursor
 constexpr int64_t RP_MAX_CAPACITY = (int64_t) 1 << 28;  // slot numbers take 28 bits of a sort key
 
 struct Table {
@@ -20,7 +18,7 @@ struct Table {
     uint32_t *box;             // [4][cap]: 65536 - rmin, 65536 - cmin, rmax + 1, cmax + 1
     i64 *isum;                 // [K][cap]
     uint32_t *imin, *imax;     // [K][cap], mirrored / biased
-    u64 cap, mask;
+    u64 cap;
     u64 *overflow;
 };
 
@@ -30,7 +28,7 @@ inline Table rp_table(void *workspace, int64_t cap, int K) {
     Table t;
     char *w = (char *) workspace;
     t.overflow = (u64 *) w;
-    w += RP_HEAD_BYTES;
+    w += LT_HEAD_BYTES;
     t.keys = (u64 *) w;      w += cap * 8;
     t.n = (u64 *) w;         w += cap * 8;
     t.sums = (u64 *) w;      w += cap * 40;
@@ -39,22 +37,15 @@ inline Table rp_table(void *workspace, int64_t cap, int K) {
     t.imin = (uint32_t *) w; w += cap * 4 * K;
     t.imax = (uint32_t *) w;
     t.cap = (u64) cap;
-    t.mask = (u64) cap - 1;
     return t;
 }
 
 inline u64 *rp_sort_buffer(void *workspace, int64_t cap, int K) {
-    return (u64 *) ((char *) workspace + RP_HEAD_BYTES + cap * rp_row_bytes(K));
-}
-
-__device__ __forceinline__ u64 rp_hash(u64 k) {  // splitmix64 finaliser
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
+    return (u64 *) ((char *) workspace + LT_HEAD_BYTES + cap * rp_row_bytes(K));
 }
 
 __device__ __forceinline__ int64_t rp_bits(double d) { return (int64_t) __double_as_longlong(d); }
 
-inline bool rp_bad_capacity(int64_t cap) { return cap < 2 || cap > RP_MAX_CAPACITY || (cap & (cap - 1)); }
+inline bool rp_bad_capacity(int64_t cap) { return lt_bad_capacity(cap, RP_MAX_CAPACITY); }
 
 }  // namespace

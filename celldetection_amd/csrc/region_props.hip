@@ -22,9 +22,10 @@
 // Minima are kept as maxima of a mirrored value, so that a zeroed table is a valid empty table:
 //   rows / columns: 65536 - r (min), r + 1 (max, the half-open end);  intensities: ~(i ^ 0x80000000) (min), i ^ 0x80000000 (max).
 //
-// Table passes: count the occupied slots; compact them as (channel << 59 | label << 28 | slot) and sort these ascending with
-// a bitonic network (1024 elements per workgroup in LDS, global steps above); finalise computes the requested columns in
-// fp64 in the order of operations include/cpn_hip.h states (this file is compiled with -ffp-contract=off).
+// Table passes: count the occupied slots; compact them (both csrc/label_table.h) as (channel << 59 | label << 28 | slot) and
+// sort these ascending with a bitonic network (1024 elements per workgroup in LDS, global steps above); finalise computes the
+// requested columns in fp64 in the order of operations include/cpn_hip.h states (this file is compiled with
+// -ffp-contract=off).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -51,30 +52,23 @@ struct Run {  // what one run or one LDS slot adds to a row
 };
 
 __device__ __noinline__ void rp_global_add(const Table &t, u64 key, const Run &a, int K) {
-    u64 h = rp_hash(key) & t.mask;
-    const u64 limit = t.cap < RP_MAX_PROBE ? t.cap : RP_MAX_PROBE;
-    for (u64 i = 0; i < limit; ++i, h = (h + 1) & t.mask) {
-        u64 cur = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0) {
-            cur = atomicCAS(&t.keys[h], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur != key) continue;
-        atomicAdd(&t.n[h], (u64) a.n);
-#pragma unroll
-        for (int q = 0; q < 5; ++q) atomicAdd(&t.sums[q * t.cap + h], a.sums[q]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) atomicMax(&t.box[q * t.cap + h], a.box[q]);
-#pragma unroll
-        for (int k = 0; k < RP_MAX_K; ++k)
-            if (k < K) {
-                atomicAdd((u64 *) &t.isum[k * t.cap + h], (u64) a.isum[k]);
-                atomicMax(&t.imin[k * t.cap + h], a.imin[k]);
-                atomicMax(&t.imax[k * t.cap + h], a.imax[k]);
-            }
+    const i64 h = lt_claim(t.keys, t.cap, key);
+    if (h < 0) {
+        atomicAdd(t.overflow, 1ull);
         return;
     }
-    atomicAdd(t.overflow, 1ull);
+    atomicAdd(&t.n[h], (u64) a.n);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) atomicAdd(&t.sums[q * t.cap + h], a.sums[q]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) atomicMax(&t.box[q * t.cap + h], a.box[q]);
+#pragma unroll
+    for (int k = 0; k < RP_MAX_K; ++k)
+        if (k < K) {
+            atomicAdd((u64 *) &t.isum[k * t.cap + h], (u64) a.isum[k]);
+            atomicMax(&t.imin[k * t.cap + h], a.imin[k]);
+            atomicMax(&t.imax[k * t.cap + h], a.imax[k]);
+        }
 }
 
 struct LdsTable {
@@ -97,14 +91,8 @@ __device__ __forceinline__ void rp_run_add(LdsTable &L, const Table &t, u64 key,
     const i64 b = (i64) a + n - 1;
     u64 sums[5] = {(u64) n * (u64) r, sc, (u64) n * (u64) r * (u64) r, (u64) r * sc, (u64) (rp_sq_sum(b) - rp_sq_sum((i64) a - 1))};
     uint32_t box[4] = {65536u - (uint32_t) r, 65536u - (uint32_t) a, (uint32_t) r + 1u, (uint32_t) b + 1u};
-    unsigned h = (unsigned) rp_hash(key) & (RP_LDS_SLOTS - 1);
-    for (int i = 0; i < RP_LDS_PROBE; ++i, h = (h + 1) & (RP_LDS_SLOTS - 1)) {
-        u64 cur = __hip_atomic_load(&L.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (cur == 0) {
-            cur = atomicCAS(&L.keys[h], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur != key) continue;
+    const int h = lt_claim_lds<RP_LDS_SLOTS, RP_LDS_PROBE>(L.keys, key);
+    if (h >= 0) {
         atomicAdd(&L.n[h], n);
 #pragma unroll
         for (int q = 0; q < 5; ++q) atomicAdd(&L.sums[q][h], sums[q]);
@@ -210,15 +198,7 @@ __global__ __launch_bounds__(256) void rp_accumulate_kernel(const int32_t *__res
             const int prr = __shfl_up(rr, 1, 64), pend = __shfl_up(ra + (int) pn, 1, 64);
             const unsigned ppn = __shfl_up(pn, 1, 64);
             const bool head = lane == 0 || pn == 0 || ppn == 0 || pcur != cur || prr != rr || pend != ra;
-            const u64 heads = __ballot(head);
-            const int seg = __popcll(heads & (~0ull >> (63 - lane)));
-            unsigned n = pn;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned on = __shfl_down(n, d, 64);
-                const int oseg = __shfl_down(seg, d, 64);
-                if (lane + d < 64 && oseg == seg) n += on;
-            }
+            const unsigned n = lt_segment_sum(head, pn);
             if (head) pn = n;
             else start &= ~(1u << ps);  // counted by the lane at the head of the joined run
         }
@@ -265,38 +245,18 @@ __global__ __launch_bounds__(256) void rp_accumulate_kernel(const int32_t *__res
 }
 
 // table -> sorted slot list -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rp_count_kernel(const u64 *__restrict__ keys, long cap, u64 *__restrict__ entries) {
-    unsigned n = 0;
-    for (long i = (long) blockIdx.x * 256 + threadIdx.x; i < cap; i += (long) gridDim.x * 256) n += keys[i] != 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(entries, (u64) n);
-}
-
 __global__ __launch_bounds__(256) void rp_fill_kernel(u64 *__restrict__ a, long n) {
     const long i = (long) blockIdx.x * 256 + threadIdx.x;
     if (i < n) a[i] = ~0ull;
 }
 
-// sort key: channel << 59 | label << 28 | slot (label < 2^31, slot < 2^28)
-__global__ __launch_bounds__(256) void rp_compact_kernel(const u64 *__restrict__ keys, long cap, u64 *__restrict__ cursor,
-                                                        u64 *__restrict__ out, long n_out) {
-    const int lane = threadIdx.x & 63;
-    const long rounds = (cap + (long) gridDim.x * 256 - 1) / ((long) gridDim.x * 256);  // uniform trip count: ballots inside
-    for (long r = 0; r < rounds; ++r) {
-        const long i = (r * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-        const u64 k = i < cap ? keys[i] : 0;
-        const u64 m = __ballot(k != 0);
-        if (m == 0) continue;
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(cursor, (u64) __popcll(m));
-        base = __shfl(base, 0, 64);
-        if (k != 0) {
-            const long pos = (long) base + __popcll(m & ((1ull << lane) - 1));
-            if (pos < n_out) out[pos] = ((k >> 32) << 59) | ((k & 0xffffffffull) << 28) | (u64) i;
-        }
+// lt_compact_kernel writes the sort key: channel << 59 | label << 28 | slot (label < 2^31, slot < 2^28)
+struct SortKeyEmit {
+    u64 *__restrict__ out;
+    __device__ void operator()(long pos, long slot, u64 k) const {
+        out[pos] = ((k >> 32) << 59) | ((k & 0xffffffffull) << 28) | (u64) slot;
     }
-}
+};
 
 // Bitonic network, ascending.  FULL: sorts every block of 1024 (k = 2 .. 1024); otherwise the steps j = 512 .. 1 of stage k.
 template <bool FULL>
@@ -428,7 +388,7 @@ extern "C" {
 int64_t cpn_props_workspace_bytes(int64_t table_capacity, int32_t intensity_channels) {
     if (rp_bad_capacity(table_capacity) || intensity_channels < 0 || intensity_channels > RP_MAX_K) return 0;
     const int64_t sort = table_capacity > 1024 ? table_capacity : 1024;
-    return RP_HEAD_BYTES + table_capacity * rp_row_bytes(intensity_channels) + sort * 8;
+    return LT_HEAD_BYTES + table_capacity * rp_row_bytes(intensity_channels) + sort * 8;
 }
 
 int32_t cpn_props_columns(const int32_t *properties, int32_t n_properties, int32_t intensity_channels) {
@@ -458,7 +418,7 @@ int cpn_props_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t ch
     if ((int64_t) H * W > 0 && (!labels || ((uintptr_t) labels & 15)))
         return cpn::fail(CPN_E_INVALID, "cpn_props_accumulate: the label image must be 16-byte aligned");
     hipStream_t st = (hipStream_t) stream;
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t) (RP_HEAD_BYTES + table_capacity * rp_row_bytes(intensity_channels)), st);
+    hipError_t e = hipMemsetAsync(workspace, 0, (size_t) (LT_HEAD_BYTES + table_capacity * rp_row_bytes(intensity_channels)), st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_props_accumulate: memset");
     if ((int64_t) H * W == 0) return 0;
     const Table t = rp_table(workspace, table_capacity, intensity_channels);
@@ -483,16 +443,7 @@ int cpn_props_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t ch
 int cpn_props_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream) {
     if (!workspace || !status_host || rp_bad_capacity(table_capacity))
         return cpn::fail(CPN_E_INVALID, "cpn_props_table_status: bad arguments");
-    hipStream_t st = (hipStream_t) stream;
-    u64 *head = (u64 *) workspace;
-    hipError_t e = hipMemsetAsync(head + 1, 0, 8, st);
-    if (e != hipSuccess) return cpn::check_hip(e, "cpn_props_table_status: memset");
-    const unsigned blocks = (unsigned) ((table_capacity + 255) / 256 < 4096 ? (table_capacity + 255) / 256 : 4096);
-    hipLaunchKernelGGL(rp_count_kernel, dim3(blocks), dim3(256), 0, st, head + RP_HEAD_BYTES / 8, (long) table_capacity, head + 1);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(status_host, head, 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return cpn::check_hip(e, "cpn_props_table_status");
+    return cpn::check_hip(lt_status(workspace, table_capacity, status_host, (hipStream_t) stream), "cpn_props_table_status");
 }
 
 int cpn_props_compact_sort(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, void *stream) {
@@ -507,9 +458,8 @@ int cpn_props_compact_sort(void *workspace, int64_t table_capacity, int32_t inte
     hipError_t e = hipMemsetAsync(head + 2, 0, 8, st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_props_compact_sort: memset");
     hipLaunchKernelGGL(rp_fill_kernel, dim3((unsigned) ((M + 255) / 256)), dim3(256), 0, st, buf, (long) M);
-    const unsigned blocks = (unsigned) ((table_capacity + 255) / 256 < 4096 ? (table_capacity + 255) / 256 : 4096);
-    hipLaunchKernelGGL(rp_compact_kernel, dim3(blocks), dim3(256), 0, st, head + RP_HEAD_BYTES / 8, (long) table_capacity, head + 2,
-                       buf, (long) entries);
+    hipLaunchKernelGGL(lt_compact_kernel<SortKeyEmit>, dim3(lt_scan_blocks(table_capacity)), dim3(256), 0, st, lt_keys(workspace),
+                       (long) table_capacity, head + 2, SortKeyEmit{buf}, (long) entries);
     hipLaunchKernelGGL((rp_bitonic_local_kernel<true>), dim3((unsigned) (M / 1024)), dim3(512), 0, st, buf, (u64) 0);
     for (int64_t k = 2048; k <= M; k <<= 1) {
         for (int64_t j = k >> 1; j >= 1024; j >>= 1)

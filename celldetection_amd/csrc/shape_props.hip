@@ -43,7 +43,6 @@ constexpr int SP_LH = SP_TILE_H + 2 * SP_HALO, SP_LW = SP_TILE_W + 2 * SP_HALO; 
 constexpr int SP_BH = SP_TILE_H + 2, SP_BW = SP_TILE_W + 2;                      // border flags: tile + 1
 constexpr int SP_LDS_SLOTS = 64, SP_LDS_PROBE = 16;
 constexpr int SP_MAX_PROPS = 64;
-constexpr int64_t SP_HEAD_BYTES = 64;
 constexpr int SP_COUNTS = 7;  // n1, n2, n3, Nv | Nh, Nd, Na
 
 struct Shape {  // the shape workspace, indexed by the slot of the property table
@@ -55,7 +54,7 @@ struct Shape {  // the shape workspace, indexed by the slot of the property tabl
 
 Shape sp_shape(void *workspace, int64_t cap) {
     Shape s;
-    char *w = (char *) workspace + SP_HEAD_BYTES;
+    char *w = (char *) workspace + LT_HEAD_BYTES;
     s.euler = (i64 *) w;      w += cap * 8;
     s.row_begin = (i64 *) w;  w += cap * 8;
     s.counts = (uint32_t *) w;
@@ -63,25 +62,12 @@ Shape sp_shape(void *workspace, int64_t cap) {
     return s;
 }
 
-int64_t sp_bytes(int64_t cap) { return SP_HEAD_BYTES + cap * (8 + 8 + 4 * SP_COUNTS); }
+int64_t sp_bytes(int64_t cap) { return LT_HEAD_BYTES + cap * (8 + 8 + 4 * SP_COUNTS); }
 
 struct Extents {  // lo[i] = 65536 - first column (0: no pixel), hi[i] = last column + 1
     uint32_t *lo, *hi;
     i64 total;
 };
-
-// slot of `key` in the table, or -1 (read only: the accumulate pass of region_props.hip inserted every key)
-__device__ __forceinline__ i64 sp_lookup(const u64 *__restrict__ keys, u64 cap, u64 key) {
-    const u64 mask = cap - 1;
-    u64 h = rp_hash(key) & mask;
-    const u64 limit = cap < RP_MAX_PROBE ? cap : RP_MAX_PROBE;
-    for (u64 i = 0; i < limit; ++i, h = (h + 1) & mask) {
-        const u64 cur = keys[h];
-        if (cur == key) return (i64) h;
-        if (cur == 0) return -1;
-    }
-    return -1;
-}
 
 struct LdsShape {
     u64 keys[SP_LDS_SLOTS];
@@ -114,24 +100,10 @@ __device__ __forceinline__ void sp_global_extent(const Shape &s, const Table &t,
     if (hi) atomicMax(&x.hi[i], hi);
 }
 
-// the LDS slot of `key`, or -1 when the tile holds more keys than the LDS table takes
-__device__ __forceinline__ int sp_lds_slot(LdsShape &L, u64 key) {
-    unsigned h = (unsigned) rp_hash(key) & (SP_LDS_SLOTS - 1);
-    for (int i = 0; i < SP_LDS_PROBE; ++i, h = (h + 1) & (SP_LDS_SLOTS - 1)) {
-        u64 cur = __hip_atomic_load(&L.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (cur == 0) {
-            cur = atomicCAS(&L.keys[h], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur == key) return (int) h;
-    }
-    return -1;
-}
-
 template <bool HULL>
 __device__ __forceinline__ void sp_add(LdsShape &L, LdsRows *R, const Shape &s, const Table &t, const Extents &x, u64 key, u64 a, u64 b, int euler,
                                        int row_local, int r, uint32_t lo, uint32_t hi) {
-    const int h = sp_lds_slot(L, key);
+    const int h = lt_claim_lds<SP_LDS_SLOTS, SP_LDS_PROBE>(L.keys, key);
     if (h >= 0) {
         if (a) atomicAdd(&L.a[h], a);
         if (b) atomicAdd(&L.b[h], b);
@@ -142,7 +114,8 @@ __device__ __forceinline__ void sp_add(LdsShape &L, LdsRows *R, const Shape &s, 
         }
         return;
     }
-    const i64 slot = sp_lookup(t.keys, t.cap, key);
+    // the tile holds more keys than the LDS table takes; the accumulate pass of region_props.hip inserted every key
+    const i64 slot = lt_lookup(t.keys, t.cap, key);
     if (slot < 0) return;
     sp_global_counts(s, slot, a, b, euler);
     if (HULL && (lo | hi)) sp_global_extent(s, t, x, slot, r, lo, hi);
@@ -226,7 +199,7 @@ __global__ __launch_bounds__(256) void sp_accumulate_kernel(const int32_t *__res
             const u64 key = L.keys[h];
             i64 slot = -1;
             if (key != 0) {
-                slot = sp_lookup(t.keys, t.cap, key);
+                slot = lt_lookup(t.keys, t.cap, key);
                 if (slot >= 0) sp_global_counts(s, slot, L.a[h], L.b[h], L.euler[h]);
                 L.keys[h] = 0; L.a[h] = 0; L.b[h] = 0; L.euler[h] = 0;
             }

@@ -22,13 +22,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._label_input import INT32_MAX, aligned16, to_int32
 from ._lib import check, ptr, stream_ptr
 
 __all__ = ['resolve_label_channels']
 
 CROSS = 0o272  # footprint bits, bit 3 * row + column: 010 / 111 / 010
 MAX_STEPS = 8  # CPN_FLAT_MAX_STEPS of include/cpn_hip.h: synchronous steps per launch
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
 def _footprint(kernel):
@@ -72,15 +72,9 @@ def resolve_label_channels(labels, method='dilation', max_iter=999, kernel=(3, 3
     if not labels.is_cuda:
         raise RuntimeError('celldetection_amd.resolve_label_channels runs on the MI355X only (got a CPU tensor).')
     H, W, C = (int(s) for s in labels.shape)
-    if H * W > _INT32_MAX:
+    if H * W > INT32_MAX:
         raise NotImplementedError('resolve_label_channels: more than 2 ** 31 - 1 pixels')
-    x = labels
-    if x.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        if x.numel() and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
-            raise ValueError('resolve_label_channels: labels holds values that do not fit int32')
-    x = x.to(torch.int32).contiguous()
-    if x.data_ptr() % 16:
-        x = x.clone()
+    x = aligned16(to_int32(labels, 'resolve_label_channels: labels holds values that do not fit int32'))
     lib = _lib.load()
     max_iter = int(max_iter)
     status = (c_int64 * 2)()

@@ -30,12 +30,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._label_input import aligned16, to_int32, upload_numpy
 from ._lib import check, ptr, stream_ptr
+from ._tables import check_capacity, default_capacity, grow_until_it_fits
 
 __all__ = ['LabelMatcher', 'LabelMatcherList', 'label_pair_table']
 
 MAX_CHANNELS = 8
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
 def _as_device_labels(x, name):
@@ -43,16 +44,7 @@ def _as_device_labels(x, name):
     if isinstance(x, np.ndarray):
         if x.dtype.kind not in 'iub':
             raise TypeError(f'LabelMatcher: {name} must hold integers (got {x.dtype})')
-        if x.dtype == np.uint64:  # torch has no uint64 arithmetic: the range is checked here
-            if x.size and int(x.max()) > _INT32_MAX:
-                raise ValueError(f'LabelMatcher: {name} holds labels that do not fit int32')
-            x = x.astype(np.int64)
-        elif x.dtype in (np.uint16, np.uint32):
-            x = x.astype(np.int64)
-        x = torch.as_tensor(np.ascontiguousarray(x))
-        if not torch.cuda.is_available():
-            raise RuntimeError('celldetection_amd.LabelMatcher runs on the MI355X only (no GPU to upload the arrays to).')
-        x = x.cuda()
+        x = upload_numpy(x, 'LabelMatcher', f'{name} holds labels')
     if not isinstance(x, torch.Tensor):
         raise TypeError(f'LabelMatcher: {name} must be a Tensor on the GPU or a numpy array (got {type(x).__name__})')
     if not x.is_cuda:
@@ -65,20 +57,7 @@ def _as_device_labels(x, name):
         raise ValueError(f'LabelMatcher: {name} must be [H, W] or [H, W, C] (got {tuple(x.shape)})')
     if x.shape[2] < 1:
         raise ValueError(f'LabelMatcher: {name} has no channel')
-    if x.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8, torch.bool):
-        if x.numel() and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
-            raise ValueError(f'LabelMatcher: {name} holds labels that do not fit int32')
-    x = x.to(torch.int32).contiguous()
-    if x.data_ptr() % 16:
-        x = x.clone()
-    return x
-
-
-def _default_capacity(pixels):
-    cap = 1 << 12
-    while cap < pixels // 16 and cap < (1 << 21):
-        cap <<= 1
-    return cap
+    return aligned16(to_int32(x, f'LabelMatcher: {name} holds labels that do not fit int32'))
 
 
 def label_pair_table(inputs, targets, table_capacity=None, return_stats=False):
@@ -93,25 +72,20 @@ def label_pair_table(inputs, targets, table_capacity=None, return_stats=False):
         raise ValueError('LabelMatcher: inputs and targets are on different devices')
     lib = _lib.load()
     pixels = int(a.shape[0]) * int(a.shape[1])
-    cap = _default_capacity(pixels) if table_capacity is None else int(table_capacity)
-    if cap < 2 or cap & (cap - 1):
-        raise ValueError('table_capacity must be a power of two')
+    cap = default_capacity(pixels, 16) if table_capacity is None else int(table_capacity)
+    check_capacity(cap)
     status = (c_int64 * 2)()
-    grown = 0
+
+    def attempt(cap):
+        nbytes = int(lib.cpn_eval_workspace_bytes(cap, 0, 0))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        check(lib.cpn_eval_pairs(ptr(a), int(a.shape[2]), ptr(b), int(b.shape[2]), pixels, cap, ptr(ws), nbytes, stream_ptr()),
+              'eval_pairs')
+        check(lib.cpn_eval_table_status(ptr(ws), cap, status, stream_ptr()), 'eval_table_status')
+        return ws, int(status[0]), int(status[1])
+
     with torch.cuda.device(a.device):
-        while True:
-            nbytes = int(lib.cpn_eval_workspace_bytes(cap, 0, 0))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-            check(lib.cpn_eval_pairs(ptr(a), int(a.shape[2]), ptr(b), int(b.shape[2]), pixels, cap, ptr(ws), nbytes,
-                                     stream_ptr()), 'eval_pairs')
-            check(lib.cpn_eval_table_status(ptr(ws), cap, status, stream_ptr()), 'eval_table_status')
-            if int(status[0]) == 0:
-                break
-            # some inserts found no slot within their probe limit: count again in a table twice the size
-            del ws
-            cap *= 2
-            grown += 1
-        n = int(status[1])
+        ws, cap, grown, n = grow_until_it_fits(cap, attempt)
         keys = torch.empty(n, dtype=torch.int64, device=a.device)
         counts = torch.empty(n, dtype=torch.int64, device=a.device)
         check(lib.cpn_eval_compact(ptr(ws), cap, ptr(keys), ptr(counts), n, stream_ptr()), 'eval_compact')

@@ -39,27 +39,13 @@ from ctypes import c_int64
 import torch
 
 from . import _lib
+from ._label_input import INT32_MAX, check_labels, to_int32
 from ._lib import check, ptr, stream_ptr
 
 __all__ = ['labels2contours_packed', 'labels2contours', 'labels2contour_list', 'resample_contours_packed', 'resample_contours']
 
 RETR_EXTERNAL, CHAIN_APPROX_NONE = 0, 1  # cv2's enum values
 TILE = 32  # CPN_CONTOURS_TILE of include/cpn_hip.h
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
-
-
-def _check_labels(labels, name, ranks=(3,)):
-    if not isinstance(labels, torch.Tensor):
-        raise TypeError(f'{name}: labels must be a Tensor on the GPU (got {type(labels).__name__})')
-    if labels.ndim not in ranks:
-        raise ValueError(f'{name}: labels must be {" or ".join("[H, W, C]" if r == 3 else "[H, W]" for r in ranks)} '
-                         f'(got {tuple(labels.shape)})')
-    if labels.ndim == 3 and labels.shape[2] < 1:
-        raise ValueError(f'{name}: labels has no channel')
-    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
-        raise TypeError(f'{name}: labels must hold integers (got {labels.dtype})')
-    if not labels.is_cuda:
-        raise RuntimeError(f'celldetection_amd.{name} runs on the MI355X only (got a CPU tensor).')
 
 
 def _check_mode(mode, method):
@@ -72,15 +58,11 @@ def _check_mode(mode, method):
 def _trace(labels, name, timings=None):
     """-> (ids int32 [K], offsets int64 [K + 1], points int32 [P, 2], values of the fragmented objects int32 [F], unique)."""
     H, W, C = (int(s) for s in labels.shape)
-    if H * W > _INT32_MAX:
+    if H * W > INT32_MAX:
         raise NotImplementedError(f'{name}: more than 2 ** 31 - 1 pixels')
     if C > 65535:
         raise NotImplementedError(f'{name}: more than 65535 channels')
-    x = labels
-    if x.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        if x.numel() and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
-            raise ValueError(f'{name}: labels holds values that do not fit int32')
-    x = x.to(torch.int32).contiguous()
+    x = to_int32(labels, f'{name}: labels holds values that do not fit int32')
     dev = x.device
     lib = _lib.load()
     status = (c_int64 * 2)()
@@ -134,7 +116,7 @@ def labels2contours_packed(labels, mode=RETR_EXTERNAL, method=CHAIN_APPROX_NONE,
     rule is in the module text.  Only ``mode=0`` (cv2.RETR_EXTERNAL) and ``method=1`` (cv2.CHAIN_APPROX_NONE) are implemented.
     ``timings``: a dict that receives the milliseconds per pass (tools/label_contours_microbench.py)."""
     _check_mode(mode, method)
-    _check_labels(labels, 'labels2contours')
+    check_labels(labels, 'labels2contours')
     ids, offsets, points, frag = _trace(labels, 'labels2contours', timings)
     if frag.numel():
         if flag_fragmented_inplace:
@@ -159,7 +141,7 @@ def labels2contours(labels, **kwargs):
 def labels2contour_list(labels, **kwargs):
     """The reference's ``cd.data.labels2contours`` (= ``labels2contour_list``): [H, W, C] or [H, W] -> list of int32 [n, 2]."""
     _check_mode(kwargs.get('mode', RETR_EXTERNAL), kwargs.get('method', CHAIN_APPROX_NONE))
-    _check_labels(labels, 'labels2contours', ranks=(2, 3))
+    check_labels(labels, 'labels2contours', ranks=(2, 3))
     if labels.ndim == 2:
         labels = labels[..., None]  # a view: flagging reaches the caller's tensor
     _, offsets, points = labels2contours_packed(labels, **kwargs)
@@ -169,7 +151,7 @@ def labels2contour_list(labels, **kwargs):
 def _check_num(num):
     if num is None or isinstance(num, float):
         raise NotImplementedError('resample_contours: num=None or a float (ragged output lengths) is not implemented; pass an int')
-    if isinstance(num, bool) or int(num) != num or int(num) < 1 or int(num) > _INT32_MAX:
+    if isinstance(num, bool) or int(num) != num or int(num) < 1 or int(num) > INT32_MAX:
         raise ValueError(f'resample_contours: num must be a positive int (got {num!r})')
     return int(num)
 

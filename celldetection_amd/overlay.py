@@ -26,13 +26,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._label_input import INT32_MAX, INT32_MIN
 from ._lib import check, ptr, stream_ptr
 
 __all__ = ['contours2overlay', 'label_cmap', 'random_colors_hsv']
 
 TILE = 32  # CPN_OVERLAY_TILE of include/cpn_hip.h
 _SUM_BITS_LIMIT = (2 ** 32 - 1) // 255  # the kernel's sums are 32 bits wide
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
 QUALITATIVE_MAPS = ('Pastel1', 'Pastel2', 'Paired', 'Accent', 'Dark2', 'Set1', 'Set2', 'Set3', 'tab10', 'tab20', 'tab20b', 'tab20c')
 
 
@@ -83,7 +83,7 @@ def _tile_lists(lib, boxes, K, H, W):
     check(lib.cpn_overlay_bin_count(ptr(boxes), K, H, W, ptr(begin[1:]), stream_ptr()), 'overlay_bin_count')
     scan = torch.cumsum(begin, 0)  # int64
     pairs = int(scan[-1].item())
-    if pairs > _INT32_MAX:
+    if pairs > INT32_MAX:
         raise NotImplementedError(f'contours2overlay: {pairs} (tile, contour) pairs; at most 2 ** 31 - 1')
     begin = scan.to(torch.int32)
     del scan
@@ -147,7 +147,7 @@ def contours2overlay(contours, size, hue_range=(0, 180), saturation_range=(60, 1
     S = int(contours.shape[1])
     if S < 1:
         raise ValueError('contours2overlay: zero-length contour at position 0')
-    if H * W > _INT32_MAX:
+    if H * W > INT32_MAX:
         raise NotImplementedError('contours2overlay: more than 2 ** 31 - 1 pixels')
     if colors is None:
         colors = torch.as_tensor(random_colors_hsv(K, hue_range, saturation_range, value_range, ubyte=True))
@@ -240,13 +240,13 @@ def label_cmap(labels, colors='rand', zero_val=0., rgba=True, alpha=None, reduce
         raise RuntimeError('celldetection_amd.label_cmap runs on the MI355X only (got a CPU tensor).')
     H, W = int(labels.shape[0]), int(labels.shape[1])
     C = int(labels.shape[2]) if labels.ndim == 3 else 1
-    if H * W > _INT32_MAX:
+    if H * W > INT32_MAX:
         raise NotImplementedError('label_cmap: more than 2 ** 31 - 1 pixels')
     x = labels
     top = None
     if x.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8) and x.numel():
         low, top = int(x.min()), int(x.max())
-        if low < _INT32_MIN or top > _INT32_MAX:
+        if low < INT32_MIN or top > INT32_MAX:
             raise ValueError('label_cmap: labels holds values that do not fit int32')
     x = x.to(torch.int32).contiguous()
     n_rand = 1

@@ -29,7 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._label_input import INT32_MAX, aligned16, to_int32, upload_numpy
 from ._lib import PROP_CODES, PROP_NAMES, check, ptr, stream_ptr
+from ._tables import check_capacity, default_capacity, grow_until_it_fits
 
 __all__ = ['region_properties', 'labels2property_table', 'SUPPORTED', 'ALIASES']
 
@@ -38,7 +40,6 @@ ALIASES = dict(bbox_area='area_bbox', equivalent_diameter='equivalent_diameter_a
                minor_axis_length='axis_minor_length', local_centroid='centroid_local', mean_intensity='intensity_mean',
                min_intensity='intensity_min', max_intensity='intensity_max')
 MAX_CHANNELS, MAX_INTENSITY_CHANNELS, MAX_SIDE, MAX_PROPERTIES = 11, 4, 65536, 64
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
 _SHAPES = dict(bbox=(4,), centroid=(2,), centroid_local=(2,), inertia_tensor=(2, 2), inertia_tensor_eigvals=(2,))
 _INTEGER = ('label', 'bbox', 'num_pixels', 'intensity_min', 'intensity_max')
 _INTENSITY = ('intensity_mean', 'intensity_min', 'intensity_max')
@@ -57,28 +58,10 @@ def _check_integers(x, what):
 
 def _upload(x, what):
     if isinstance(x, np.ndarray):
-        if x.dtype in (np.uint16, np.uint32, np.uint64):
-            if x.size and int(x.max()) > _INT32_MAX:
-                raise ValueError(f'region_properties: {what} holds values that do not fit int32')
-            x = x.astype(np.int64 if x.dtype != np.uint16 else np.int32)
-        if not torch.cuda.is_available():
-            raise RuntimeError('celldetection_amd.region_properties runs on the MI355X only (no GPU to upload the arrays to).')
-        x = torch.as_tensor(np.ascontiguousarray(x)).cuda()
+        x = upload_numpy(x, 'region_properties', f'{what} holds values')
     if not x.is_cuda:
         raise RuntimeError('celldetection_amd.region_properties runs on the MI355X only (got a CPU tensor).')
     return x
-
-
-def _to_int32(x, what):
-    if x.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8, torch.bool):
-        if x.numel() and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
-            raise ValueError(f'region_properties: {what} holds values that do not fit int32')
-    return x.to(torch.int32)
-
-
-def _aligned(x):
-    x = x.contiguous()
-    return x.clone() if x.data_ptr() % 16 else x
 
 
 def _resolve(properties):
@@ -118,13 +101,6 @@ def _column_names(props, sep, K):
     return names, kinds
 
 
-def _default_capacity(pixels):
-    cap = 1 << 12
-    while cap < pixels // 64 and cap < (1 << 21):
-        cap <<= 1
-    return cap
-
-
 def _spacing(spacing):
     if spacing is None:
         return 1., 1.
@@ -157,7 +133,7 @@ def _accumulate(labels, intensity_image, iter_channels, table_capacity, intensit
     H, W, C = (int(s) for s in x.shape)
     if C < 1:
         raise ValueError('region_properties: labels has no channel')
-    if H * W > _INT32_MAX or max(H, W) > MAX_SIDE:
+    if H * W > INT32_MAX or max(H, W) > MAX_SIDE:
         raise NotImplementedError(f'region_properties: images of more than 2 ** 31 - 1 pixels or more than {MAX_SIDE} pixels a '
                                   f'side are not implemented (got {H} x {W})')
     if C > MAX_CHANNELS:
@@ -178,30 +154,26 @@ def _accumulate(labels, intensity_image, iter_channels, table_capacity, intensit
         if img.dtype in (torch.int8, torch.bool):
             img = img.to(torch.int16)
         elif img.dtype not in _INTENSITY_DTYPES:  # uint16 (where torch has it), int64, ...
-            img = _to_int32(img, 'intensity_image')
+            img = to_int32(img, 'region_properties: intensity_image holds values that do not fit int32')
         idt = _INTENSITY_DTYPES[img.dtype]
         img = img.contiguous()
     elif intensity_requested:
         raise AttributeError('region_properties: an intensity property was requested without an intensity_image')
-    x = _aligned(_to_int32(x, 'labels'))
+    x = aligned16(to_int32(x, 'region_properties: labels holds values that do not fit int32'))
     lib = _lib.load()
-    cap = _default_capacity(H * W) if table_capacity is None else int(table_capacity)
-    if cap < 2 or cap & (cap - 1):
-        raise ValueError('table_capacity must be a power of two')
+    cap = default_capacity(H * W, 64) if table_capacity is None else int(table_capacity)
+    check_capacity(cap)
     status = (c_int64 * 2)()
-    grown = 0
+
+    def attempt(cap):
+        nbytes = int(lib.cpn_props_workspace_bytes(cap, K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        check(lib.cpn_props_accumulate(ptr(x), H, W, C, ptr(img), K, idt, cap, ptr(ws), nbytes, stream_ptr()), 'props_accumulate')
+        check(lib.cpn_props_table_status(ptr(ws), cap, status, stream_ptr()), 'props_table_status')
+        return ws, int(status[0]), int(status[1])
+
     with torch.cuda.device(x.device):
-        while True:
-            nbytes = int(lib.cpn_props_workspace_bytes(cap, K))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            check(lib.cpn_props_accumulate(ptr(x), H, W, C, ptr(img), K, idt, cap, ptr(ws), nbytes, stream_ptr()), 'props_accumulate')
-            check(lib.cpn_props_table_status(ptr(ws), cap, status, stream_ptr()), 'props_table_status')
-            if int(status[0]) == 0:
-                break
-            del ws  # some inserts found no slot within their probe limit: accumulate again in a table twice the size
-            cap *= 2
-            grown += 1
-        n = int(status[1])
+        ws, cap, grown, n = grow_until_it_fits(cap, attempt)
         check(lib.cpn_props_compact_sort(ptr(ws), cap, K, n, stream_ptr()), 'props_compact_sort')
     acc = _Accumulated()
     acc.x, acc.H, acc.W, acc.C, acc.K, acc.img_dtype, acc.ws, acc.cap, acc.grown, acc.rows = x, H, W, C, K, img_dtype, ws, cap, grown, n

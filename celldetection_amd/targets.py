@@ -39,23 +39,17 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._label_input import INT32_MAX, INT32_MIN, check_labels, to_int32
 from ._lib import check, ptr, stream_ptr
+from ._tables import default_capacity
 from .fourier import _check_order, efd_packed
-from .label_contours import _check_labels, _split, labels2contours_packed, resample_contours_packed
+from .label_contours import _split, labels2contours_packed, resample_contours_packed
 
 __all__ = ['labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator']
 
 DIST_L1, DIST_L2, DIST_C = 1, 2, 3  # CPN_DIST_* of include/cpn_hip.h = cv2's enum values
 MAX_STEPS = 8  # CPN_LABEL_DISTANCES_MAX_STEPS: synchronous steps per launch
 MAX_SIDE = 32768
-_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
-_SMALL = (torch.int32, torch.int16, torch.int8, torch.uint8)
-
-
-def _as_int32(x, name):
-    if x.dtype not in _SMALL and x.numel() and (int(x.min()) < _INT32_MIN or int(x.max()) > _INT32_MAX):
-        raise ValueError(f'{name}: labels holds values that do not fit int32')
-    return x.to(torch.int32).contiguous()
 
 
 def labels2distances(labels, distance_type=DIST_L2, overlap_zero=True, per_instance=True, protected_size=36,
@@ -69,14 +63,14 @@ def labels2distances(labels, distance_type=DIST_L2, overlap_zero=True, per_insta
     if not overlap_zero:
         raise NotImplementedError('labels2distances: overlap_zero=False is not implemented (the reference result depends on the '
                                   'order in which objects overwrite shared pixels)')
-    if isinstance(protected_size, bool) or int(protected_size) != protected_size or not 0 <= int(protected_size) <= _INT32_MAX:
+    if isinstance(protected_size, bool) or int(protected_size) != protected_size or not 0 <= int(protected_size) <= INT32_MAX:
         raise ValueError(f'labels2distances: protected_size must be a non-negative int (got {protected_size!r})')
-    _check_labels(labels, 'labels2distances', ranks=(2, 3))
+    check_labels(labels, 'labels2distances', ranks=(2, 3))
     x = labels[..., None] if labels.ndim == 2 else labels
     H, W, C = (int(s) for s in x.shape)
     if H > MAX_SIDE or W > MAX_SIDE:
         raise NotImplementedError(f'labels2distances: H and W are at most {MAX_SIDE}')
-    x = _as_int32(x, 'labels2distances')
+    x = to_int32(x, 'labels2distances: labels holds values that do not fit int32')
     dev = x.device
     lib = _lib.load()
     status = (c_int64 * 2)()
@@ -100,9 +94,7 @@ def labels2distances(labels, distance_type=DIST_L2, overlap_zero=True, per_insta
             active.append(int(status[1]))
             if int(status[0]) == 0:
                 break
-        cap = 1 << 12
-        while cap < H * W // 64 and cap < (1 << 21):
-            cap *= 2
+        cap = default_capacity(H * W, 64)
         while True:
             table = torch.empty(int(lib.cpn_label_distances_table_bytes(cap)), dtype=torch.uint8, device=dev)
             check(lib.cpn_label_distances_reduce(H, W, ptr(ws), nbytes, ptr(table), cap, status, stream_ptr()),
@@ -123,7 +115,7 @@ def labels2distances(labels, distance_type=DIST_L2, overlap_zero=True, per_insta
 
 def _inplace_int32(labels, name, fn):
     """Runs fn on an int32 contiguous image of ``labels`` and writes the result back when that image is a copy."""
-    x = _as_int32(labels, name)
+    x = to_int32(labels, f'{name}: labels holds values that do not fit int32')
     fn(x)
     if x.data_ptr() != labels.data_ptr() or x.dtype != labels.dtype:
         labels.copy_(x)
@@ -138,7 +130,7 @@ def mask_labels_by_distance_(labels, distances, max_bg_dist, min_fg_dist, return
         raise TypeError('mask_labels_by_distance_: distances must be a float Tensor on the GPU')
     if isinstance(labels, torch.Tensor) and labels.ndim == 3 and tuple(distances.shape) != tuple(labels.shape[:2]):
         raise ValueError(f'mask_labels_by_distance_: distances must be {tuple(labels.shape[:2])} (got {tuple(distances.shape)})')
-    _check_labels(labels, 'mask_labels_by_distance_')
+    check_labels(labels, 'mask_labels_by_distance_')
     if not distances.is_cuda or distances.device != labels.device:
         raise RuntimeError('celldetection_amd.mask_labels_by_distance_ runs on the MI355X only (distances on another device).')
     H, W, C = (int(s) for s in labels.shape)
@@ -189,7 +181,7 @@ def filter_instances_(labels, partials=True, partials_border=1, min_area=4, max_
     ``max_area`` elements (counted over all channels) become ``constant``; with ``continuous`` the label gaps are filled.  The
     table of values is built with stock tensor operations, the image is rewritten by one HIP pass.  The two departures from
     the reference are in the module text."""
-    _check_labels(labels, 'filter_instances_', ranks=(2, 3))
+    check_labels(labels, 'filter_instances_', ranks=(2, 3))
     if labels.numel() == 0:
         return labels
     uni, cnt = torch.unique(labels, return_counts=True)
@@ -204,7 +196,7 @@ def filter_instances_(labels, partials=True, partials_border=1, min_area=4, max_
     if not change.any():
         return labels
     info = torch.iinfo(labels.dtype)
-    if new.min() < max(info.min, _INT32_MIN) or new.max() > min(info.max, _INT32_MAX):
+    if new.min() < max(info.min, INT32_MIN) or new.max() > min(info.max, INT32_MAX):
         raise ValueError(f'filter_instances_: constant {constant!r} does not fit {labels.dtype}')
     keys = torch.as_tensor(uni_h[change], dtype=torch.int32).to(labels.device)  # ascending: torch.unique sorts
     values = torch.as_tensor(new[change], dtype=torch.int32).to(labels.device)
@@ -247,7 +239,7 @@ class CPNTargetGenerator:
         """``labels``: one label image, Tensor[H, W, C] or [H, W] on the GPU; it is filtered and flagged in place.  ``kwargs`` go
         to ``labels2distances``."""
         self._reset()
-        _check_labels(labels, 'CPNTargetGenerator.feed', ranks=(2, 3))
+        check_labels(labels, 'CPNTargetGenerator.feed', ranks=(2, 3))
         if labels.ndim == 2:
             labels = labels[..., None]
         filter_instances_(labels, partials=self.remove_partials, partials_border=border, min_area=min_area, max_area=max_area,

@@ -492,7 +492,7 @@ int cpn_labels_round(const int32_t *points, const int32_t *boxes, int64_t K, int
  *                    (input label, target label) pair (a pixel counts once per pair), under (label << 32) the elements of
  *                    every input label and under (label) those of every target label.  Asynchronous.
  *   table_status:    status_host[0] = inserts that found no slot (> 0: repeat cpn_eval_pairs with a larger table),
- *                    [1] = occupied slots.  Synchronises the stream.
+ *                    [1] = occupied slots.  Synchronises the stream.  May be repeated: every call counts afresh.
  *   compact:         the occupied slots -> keys / counts (int64 [entries], device) in no particular order.
  *   unions:          for the pairs (sorted keys): position of both labels in the sorted label lists and
  *                    unions = input count + target count - intersection.  Synchronises the stream.
@@ -557,7 +557,7 @@ int cpn_flat_finish(int32_t *lbl, int32_t H, int32_t W, void *workspace, int64_t
  *                    c^2 over global pixel coordinates, the bounding box and per intensity channel sum, minimum and
  *                    maximum.  Asynchronous.
  *   table_status:    status_host[0] = inserts that found no slot (> 0: repeat accumulate with a larger table),
- *                    [1] = occupied slots = rows.  Synchronises the stream.
+ *                    [1] = occupied slots = rows.  Synchronises the stream.  May be repeated: every call counts afresh.
  *   compact_sort:    orders the occupied slots by (channel, label) ascending inside the workspace.  Asynchronous.
  *   finalise:        out: int64 [out_columns][entries] on the device with out_columns = columns + 1: one row per column in
  *                    the order of the property list (vectors and matrices in row-major order, intensity properties one

@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import celldetection_amd as cda  # noqa: E402
 from celldetection_amd import _lib  # noqa: E402
-from celldetection_amd.instance_eval import _as_device_labels, _default_capacity  # noqa: E402
+from celldetection_amd._tables import default_capacity  # noqa: E402
+from celldetection_amd.instance_eval import _as_device_labels  # noqa: E402
 
 HBM_COPY_TBS = 6.29  # measured float4 copy rate of the MI355X (spec 8.0 TB/s)
 
@@ -64,7 +65,7 @@ def main():
     a, b = _as_device_labels(a, 'inputs'), _as_device_labels(b, 'targets')
     lib = _lib.load()
     pixels = size * size
-    cap = _default_capacity(pixels)
+    cap = default_capacity(pixels, 16)
     nbytes = int(lib.cpn_eval_workspace_bytes(cap, 0, 0))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     run = lambda: _lib.check(lib.cpn_eval_pairs(_lib.ptr(a), int(a.shape[2]), _lib.ptr(b), int(b.shape[2]), pixels, cap,

@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import celldetection_amd as cda  # noqa: E402
 from celldetection_amd import _lib  # noqa: E402
-from celldetection_amd.region_props import _default_capacity  # noqa: E402
+from celldetection_amd._tables import default_capacity  # noqa: E402
 from eval_microbench import contours  # noqa: E402
 from flat_labels_microbench import event_ms  # noqa: E402
 
@@ -69,7 +69,7 @@ def one(size, objects, repeats, radius, channels, dev):
         labels = torch.cat((labels, labels.new_zeros((size, size, channels - made))), 2).contiguous()
     H, W, C = (int(s) for s in labels.shape)
     lib = _lib.load()
-    cap = _default_capacity(H * W)
+    cap = default_capacity(H * W, 64)
     res = dict(size=size, objects_asked=objects, radius=radius, channels=C, channels_made=made, bytes_read=H * W * C * 4)
     cols, stats = cda.region_properties(labels, PROPS, return_stats=True)
     cap = stats['table_capacity']
