@@ -199,6 +199,9 @@ struct Validator {
             return fail(CPN_E_INVALID, "cpn_plan_create: a conv without a destination tensor writes external output out_index = 0 .. 4");
         if ((conv || o.op == CPN_OP_MAXPOOL) && (o.kh < 1 || o.kw < 1 || o.stride < 1 || o.pad < 0 || (conv && o.bundles < 1)))
             return fail(CPN_E_INVALID, "cpn_plan_create: conv / max-pool ops need kh, kw, stride >= 1, pad >= 0 (convs: bundles >= 1)");
+        // (as torch.nn.MaxPool2d: with more padding a window can lie in the padding alone, and its maximum is -inf)
+        if (o.op == CPN_OP_MAXPOOL && (o.pad > o.kh / 2 || o.pad > o.kw / 2))
+            return fail(CPN_E_INVALID, "cpn_plan_create: a max-pool's pad must be at most half its kernel size");
         return 0;
     }
 };

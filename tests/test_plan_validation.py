@@ -208,6 +208,7 @@ def test_planning_rejects(case):
 MSG_IDS = 'cpn_plan_create: op without the source / destination tensor its kind needs'
 MSG_OUT = 'cpn_plan_create: a conv without a destination tensor writes external output out_index = 0 .. 4'
 MSG_GEOMETRY = 'cpn_plan_create: conv / max-pool ops need kh, kw, stride >= 1, pad >= 0 (convs: bundles >= 1)'
+MSG_POOL_PAD = "cpn_plan_create: a max-pool's pad must be at most half its kernel size"
 INDEX_CASES = [
     ('id_below_minus_one', 'u22', 'bf16', op(**PLAIN3), 'res', -2, 'cpn_plan_create: tensor id out of range'),
     ('id_below_minus_one_dst', 'u22', 'bf16', op(**PLAIN3), 'dst', -7, 'cpn_plan_create: tensor id out of range'),
@@ -229,6 +230,8 @@ INDEX_CASES = [
     ('maxpool_kernel', 'u22', 'bf16', op(op=POOL), 'kh', 0, MSG_GEOMETRY),
     ('maxpool_stride', 'u22', 'bf16', op(op=POOL), 'stride', 0, MSG_GEOMETRY),
     ('maxpool_pad', 'u22', 'bf16', op(op=POOL), 'pad', -1, MSG_GEOMETRY),
+    # (accepted before: a 2 x 2 window two pixels into the padding holds no valid tap, its maximum is -inf | -448 x scale)
+    ('maxpool_pad_beyond_half_kernel', 'u22', 'bf16', op(op=POOL), 'pad', 2, MSG_POOL_PAD),
 ]
 
 
