@@ -36,6 +36,9 @@ SHAPE_CODES = {name: code for code, name in enumerate(SHAPE_NAMES)}
 # training objective (CPN_OBJECTIVE_* of include/cpn_hip.h)
 OBJECTIVE_MAX_ITERATIONS, OBJECTIVE_META_WORDS = 64, 2
 OBJECTIVE_FLAG_LABEL_RANGE, OBJECTIVE_FLAG_LABEL_ROWS, OBJECTIVE_FLAG_CLASS_RANGE = 1, 2, 4
+# component labelling (CPN_COMPONENTS_* of include/cpn_hip.h)
+COMPONENTS_EQUAL, COMPONENTS_NONZERO = 0, 1
+COMPONENTS_MODES = {'equal': COMPONENTS_EQUAL, 'nonzero': COMPONENTS_NONZERO}
 
 
 class TensorDesc(Structure):
@@ -226,6 +229,9 @@ _SIGNATURES = [
     ('cpn_objective_workspace_bytes', c_int64, [POINTER(ObjectiveArgs), c_int64]),
     ('cpn_objective_proposals', ctypes.c_int, [POINTER(ObjectiveArgs), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                                c_int64, c_void_p, c_void_p]),
+    ('cpn_components_workspace_bytes', c_int64, [c_int32, c_int32, c_int32]),
+    ('cpn_components_label', ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                            c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -39,6 +39,8 @@ SOURCES = {
     # integer components and border following; the fp64 resampling is defined by its order of operations: no FMA contraction
     # (fp64 sqrt and division are correctly rounded as they stand)
     'label_contours.hip': ['-ffp-contract=off'],
+    # integer only: the components pass shared with label_contours.hip (csrc/components.h) and the numbering
+    'components.hip': [],
     # fp64 sums whose result is defined by their order of operations (csrc/efd_chunks.h): no FMA contraction
     'contour_fourier.hip': ['-ffp-contract=off'],
     # integer chamfer relaxation; the float32 normalisation is one IEEE division per pixel: correctly rounded, no contraction
@@ -54,7 +56,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -8,20 +8,10 @@
 // another component of the same value counts as a component (cv2.findContours(RETR_EXTERNAL) would not see it).  Contours are
 // returned by ascending value; of a value that is unfragmented in several channels the highest channel is returned.
 //
-// Components (three launches, all channels at once; roots = int32 [C][H][W], 4 B per pixel and channel).
-//   lc_local_kernel:   a workgroup owns a 32 x 32 tile of one channel and runs a union-find in LDS over the links of every pixel
-//                      to its W, NW, N and NE neighbour of equal value (those that follow from other pixels' links left out); it writes the image index (y * W + x) of the pixel's local
-//                      root, -1 for values <= 0.
-//   lc_seam_kernel:    one thread per pixel of a tile's first column or first row links it to its (up to three) neighbours of equal
-//                      value in the tile to the left or above.  Every access to a parent word in this launch is an agent-scope atomic
-//                      (relaxed loads, atomicMin): no plain load reads a word that another workgroup writes, and no workgroup waits
-//                      for another.  A stale parent is still an ancestor, so freshness is not needed for correctness, atomicity is.
-//   lc_flatten_kernel: every pixel follows its chain to the root and stores it (atomic loads and stores again: chains are shortened
-//                      under the readers, and either value is an ancestor); root words are never written.  Counts the roots.
-// The larger index is always linked under the smaller (atomicMin on the parent word), so parent <= self everywhere, every chain
-// strictly decreases (the bound of every find loop), a union either ends or continues with a strictly smaller maximum of its two
-// indices (the bound of the union loop), and the root of a component is its smallest image index: its raster-first pixel, where
-// the border following has to start.
+// Components (csrc/components.h, shared with csrc/components.hip; three launches, all channels at once; roots = int32 [C][H][W],
+// 4 B per pixel and channel): the 8-connected equal-value instantiation of the tile union-find, the seam merge with agent-scope
+// atomicMin and the flattening pass.  parent <= self everywhere and the root of a component is its smallest image index: its
+// raster-first pixel, where the border following has to start.
 //
 // Object table (cpn_contours_table).  lc_compact_kernel gives every root a slot (key = value << 32 | channel, root) and replaces
 // the root's own word by -2 - slot; lc_count_kernel counts the pixels per slot (one atomic per wave and slot); rocprim sorts the
@@ -46,6 +36,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "../../include/cpn_hip.h"
+#include "components.h"
 #include "contour_trace.h"
 #include "cpn_error.h"
 
@@ -53,121 +44,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int LC_T = CPN_CONTOURS_TILE, LC_SHIFT = 5;
-static_assert((1 << LC_SHIFT) == LC_T && LC_T * LC_T == 1024, "tile geometry: 256 threads own 4 pixels each");
 constexpr int LC_COUNTERS = 8;  // u64 each: [0] roots, [1] slots given, [2] fragmented entries, [3] traces that reached the cap
-
-constexpr int SCOPE_WG = __HIP_MEMORY_SCOPE_WORKGROUP, SCOPE_AGENT = __HIP_MEMORY_SCOPE_AGENT;
-
-// parent <= self: the chain strictly decreases, so the loop ends after at most x steps
-template <int SCOPE>
-__device__ __forceinline__ int uf_find(int *L, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(L + x, __ATOMIC_RELAXED, SCOPE);
-        if (p >= x || p < 0) return x;
-        x = p;
-    }
-}
-
-// links the trees of a and b: the larger root under the smaller.  max(a, b) strictly decreases from one round to the next.
-template <int SCOPE>
-__device__ __forceinline__ void uf_union(int *L, int a, int b) {
-    for (;;) {
-        a = uf_find<SCOPE>(L, a);
-        b = uf_find<SCOPE>(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
-        if (old >= a || old < 0) return;  // a was a root and now hangs under b
-        a = old;                           // a had been linked under old < a meanwhile: go on with (old, b)
-    }
-}
-
-__global__ __launch_bounds__(256) void lc_local_kernel(const int32_t *__restrict__ labels, int C, int H, int W, int tiles_x,
-                                                      long HW, int32_t *__restrict__ roots) {
-    __shared__ int32_t val[LC_T * LC_T];
-    __shared__ int par[LC_T * LC_T];
-    const int c = blockIdx.y, tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * LC_T, x0 = tx * LC_T, tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = tid + 256 * k, y = y0 + (i >> LC_SHIFT), x = x0 + (i & (LC_T - 1));
-        const int32_t v = y < H && x < W ? labels[((long) y * W + x) * C + c] : 0;
-        val[i] = v;
-        par[i] = v > 0 ? i : -1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = tid + 256 * k, ly = i >> LC_SHIFT, lx = i & (LC_T - 1);
-        const int32_t v = val[i];
-        if (v <= 0) continue;
-        // links that other pixels make are left out: with N equal, NW - N and N - NE are W links of N and NE; with W equal,
-        // NW - W is the N link of W
-        const bool w_eq = lx > 0 && val[i - 1] == v, n_eq = ly > 0 && val[i - LC_T] == v;
-        if (w_eq) uf_union<SCOPE_WG>(par, i, i - 1);
-        if (n_eq) uf_union<SCOPE_WG>(par, i, i - LC_T);
-        if (ly > 0 && !n_eq) {
-            if (lx > 0 && !w_eq && val[i - LC_T - 1] == v) uf_union<SCOPE_WG>(par, i, i - LC_T - 1);
-            if (lx < LC_T - 1 && val[i - LC_T + 1] == v) uf_union<SCOPE_WG>(par, i, i - LC_T + 1);
-        }
-    }
-    __syncthreads();
-    int32_t *out = roots + (long) c * HW;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = tid + 256 * k, y = y0 + (i >> LC_SHIFT), x = x0 + (i & (LC_T - 1));
-        if (y < H && x < W) {
-            int r = -1;
-            if (val[i] > 0) {
-                const int l = uf_find<SCOPE_WG>(par, i);
-                r = (y0 + (l >> LC_SHIFT)) * W + x0 + (l & (LC_T - 1));
-            }
-            out[(long) y * W + x] = r;
-        }
-    }
-}
-
-// seam pixels: first the (tiles_x - 1) * H pixels of the tiles' first columns, then the (tiles_y - 1) * W of their first rows
-__global__ __launch_bounds__(256) void lc_seam_kernel(const int32_t *__restrict__ labels, int C, int H, int W, int tiles_x,
-                                                     long n_col, long n_seam, long HW, int32_t *roots) {
-    const long i = (long) blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_seam) return;
-    const int c = blockIdx.y;
-    int x, y, dxs, dys;  // the three neighbours: (x - 1, y + k) for a column pixel, (x + k, y - 1) for a row pixel, k = -1, 0, 1
-    if (i < n_col) {
-        x = (int) (i / H + 1) * LC_T;
-        y = (int) (i % H);
-        dxs = 0; dys = 1;
-    } else {
-        const long j = i - n_col;
-        y = (int) (j / W + 1) * LC_T;
-        x = (int) (j % W);
-        dxs = 1; dys = 0;
-    }
-    const int32_t v = labels[((long) y * W + x) * C + c];
-    if (v <= 0) return;
-    int *L = roots + (long) c * HW;
-    for (int k = -1; k <= 1; ++k) {
-        const int xx = dys ? x - 1 : x + k * dxs, yy = dys ? y + k : y - 1;
-        if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
-        if (labels[((long) yy * W + xx) * C + c] == v) uf_union<SCOPE_AGENT>(L, y * W + x, yy * W + xx);
-    }
-}
-
-__global__ __launch_bounds__(256) void lc_flatten_kernel(long HW, int32_t *roots, u64 *__restrict__ counters) {
-    const long p = (long) blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
-    int *L = roots + (long) blockIdx.y * HW;
-    const int first = __hip_atomic_load(L + p, __ATOMIC_RELAXED, SCOPE_AGENT);
-    if (first < 0) return;
-    if (first == (int) p) {
-        atomicAdd(&counters[0], (u64) 1);  // (one add per wave: the compiler merges the lanes)
-        return;
-    }
-    const int r = uf_find<SCOPE_AGENT>(L, first);
-    if (r != first) __hip_atomic_store(L + p, r, __ATOMIC_RELAXED, SCOPE_AGENT);
-}
 
 __global__ __launch_bounds__(256) void lc_compact_kernel(const int32_t *__restrict__ labels, int C, long HW, int32_t *roots, long n,
                                                         u64 *__restrict__ keys, uint32_t *__restrict__ vals,
@@ -388,17 +265,7 @@ int cpn_contours_components(const int32_t *labels, int32_t channels, int32_t H, 
     u64 *counters = (u64 *) workspace;
     hipError_t e = hipMemsetAsync(counters, 0, LC_COUNTERS * 8, st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_contours_components: memset");
-    const int tiles_x = (W + LC_T - 1) >> LC_SHIFT, tiles_y = (H + LC_T - 1) >> LC_SHIFT;
-    const long tiles = (long) tiles_x * tiles_y;
-    hipLaunchKernelGGL(lc_local_kernel, dim3((unsigned) tiles, (unsigned) channels), dim3(256), 0, st, labels, channels, H, W,
-                       tiles_x, HW, roots);
-    const long n_col = (long) (tiles_x - 1) * H, n_seam = n_col + (long) (tiles_y - 1) * W;
-    if (n_seam > 0)
-        hipLaunchKernelGGL(lc_seam_kernel, dim3((unsigned) ((n_seam + 255) / 256), (unsigned) channels), dim3(256), 0, st, labels,
-                           channels, H, W, tiles_x, n_col, n_seam, HW, roots);
-    hipLaunchKernelGGL(lc_flatten_kernel, dim3((unsigned) ((HW + 255) / 256), (unsigned) channels), dim3(256), 0, st, HW, roots,
-                       counters);
-    e = hipGetLastError();
+    e = cc_components_pass<8, CC_EQUAL>(labels, channels, 1, channels, H, W, roots, counters, st);
     if (e != hipSuccess) return cpn::check_hip(e, "cpn_contours_components");
     u64 host[LC_COUNTERS];
     if (const int rc = lc_read_counters(counters, host, st, "cpn_contours_components: status")) return rc;

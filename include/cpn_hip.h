@@ -711,7 +711,8 @@ int cpn_label_cmap(const int32_t *labels, int64_t pixels, int32_t channels, int3
 
 /* ----------------------------------------------------------------------------------------------------------
  * Contours of label images (cd.data.labels2contours / labels2contour_list, celldetection/data/cpn.py:93-144, and
- * cd.data.resample_contours, celldetection/data/misc.py:371-405; csrc/label_contours.hip, csrc/contour_trace.h).  ABI 20.
+ * cd.data.resample_contours, celldetection/data/misc.py:371-405; csrc/label_contours.hip, csrc/components.h,
+ * csrc/contour_trace.h).  ABI 20.
  * labels: int32 [H][W][channels] on the device, channel-interleaved, channels <= 65535, H * W <= 2^31 - 1 (CPN_E_UNSUPPORTED
  * above).  Rule: an object is a pair (channel, value v > 0); values <= 0 take no part.  Its components are the 8-connected sets
  * of pixels of that channel holding v.  An object with exactly one component yields one contour: Suzuki-Abe border following of
@@ -933,6 +934,45 @@ int cpn_objective_head(const CpnObjectiveArgs *args, int32_t *indices, int32_t *
 int64_t cpn_objective_workspace_bytes(const CpnObjectiveArgs *args, int64_t P);
 int cpn_objective_proposals(const CpnObjectiveArgs *args, const int32_t *indices, int32_t P, const int32_t *meta, int32_t present,
                             void *head_workspace, void *workspace, int64_t workspace_bytes, float *out, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Component labelling (cd.data.relabel_ / stack_labels, celldetection/data/segmentation.py:106-150, and cd.data.masks2labels,
+ * celldetection/data/cpn.py:147-176; csrc/components.hip, csrc/components.h, csrc/component_rank.h).  Additions to ABI 22.
+ * This text is the contract.
+ *
+ * The rule.  The image holds int32 elements (y, x, c) at in[(y * W + x) * pixel_stride + c * channel_stride]; a channel is
+ * labelled on its own.  A pixel takes part if it is foreground.  Two neighbouring foreground pixels are linked if they are equal:
+ *   CPN_COMPONENTS_EQUAL    foreground is v > 0, equal is the same value;
+ *   CPN_COMPONENTS_NONZERO  foreground is v != 0, any two foreground pixels are equal.
+ * Neighbours are the 4 edge neighbours (connectivity 4) or the 8 neighbours (connectivity 8).  A component is a class of the
+ * transitive closure of the links.  Components are numbered first + 0, first + 1, ... by channel ascending and, within a
+ * channel, by the raster index y * W + x of their first pixel (the smallest one).  Every pixel of a component receives the
+ * component's number.  Pixels that take no part keep their value: zeros, and in EQUAL mode negatives.  counts = int32
+ * [channels] on the device receives the number of components per channel.
+ * This is skimage.measure.label(background=0) per channel (connectivity 8 = skimage's full connectivity in 2-D, which the
+ * reference's relabel_ uses) with a numbering that runs on across the channels.  relabel_ skips every component that holds a
+ * negative pixel; under the equal-value rule these are exactly the components of negative value: untouched and uncounted.
+ * cv2.connectedComponents (masks2labels) is NONZERO mode per mask; for connectivity 8 OpenCV's default algorithm scans 2 x 2
+ * blocks and may number the components of one mask in another order: the partition and the set of labels per mask are the
+ * contract there, the order within a mask (raster-first, for both connectivities) is this library's own.
+ *
+ * Layouts: channel-interleaved (channel_stride 1, pixel_stride >= channels; the [H][W][C] label image is (C, 1)) or planar
+ * (pixel_stride 1, channel_stride >= H * W; a [N][H][W] mask stack is (1, H * W)), for in and out independently; other strides
+ * are CPN_E_INVALID.  out may be in (in place, same strides): then only the pixels that take part are written.
+ * channels <= 65535, H * W <= 2^31 - 1, channels * ceil(H * W / 256) <= 2^31 - 2 (CPN_E_UNSUPPORTED above;
+ * cpn_components_workspace_bytes returns 0 for arguments the call refuses); connectivity 4 or 8; first >= 1.
+ * workspace: cpn_components_workspace_bytes(channels, H, W) bytes on the device (counters, the roots image of 4 B per pixel and
+ * channel, two 8-byte words per 256 pixels, the scan's scratch).
+ * More than 2^31 - 1 components, or first + components - 1 > 2^31 - 1, is CPN_E_UNSUPPORTED: nothing is written to out, no value
+ * wraps.  Integer arithmetic only and no value-carrying atomics: results are bit-identical from run to run.  The call
+ * synchronises the stream once (it reads the total before it numbers).  H * W = 0 zeroes counts and does nothing else.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_COMPONENTS_EQUAL 0
+#define CPN_COMPONENTS_NONZERO 1
+int64_t cpn_components_workspace_bytes(int32_t channels, int32_t H, int32_t W);
+int cpn_components_label(const int32_t *in, int64_t pixel_stride, int64_t channel_stride, int32_t channels, int32_t H, int32_t W,
+                         int32_t connectivity, int32_t mode, int32_t first, int32_t *out, int64_t out_pixel_stride,
+                         int64_t out_channel_stride, int32_t *counts, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }
