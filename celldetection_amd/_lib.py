@@ -39,6 +39,10 @@ OBJECTIVE_FLAG_LABEL_RANGE, OBJECTIVE_FLAG_LABEL_ROWS, OBJECTIVE_FLAG_CLASS_RANG
 # component labelling (CPN_COMPONENTS_* of include/cpn_hip.h)
 COMPONENTS_EQUAL, COMPONENTS_NONZERO = 0, 1
 COMPONENTS_MODES = {'equal': COMPONENTS_EQUAL, 'nonzero': COMPONENTS_NONZERO}
+# trainable convolution (CPN_CONV_PACK_* and the dtype codes of include/cpn_hip.h)
+CONV_PACK_FORWARD, CONV_PACK_DGRAD = 0, 1
+CONV_PACK_MODES = {'forward': CONV_PACK_FORWARD, 'dgrad': CONV_PACK_DGRAD}
+CONV_TRAIN_F32, CONV_TRAIN_BF16 = 0, 1
 
 
 class TensorDesc(Structure):
@@ -232,6 +236,11 @@ _SIGNATURES = [
     ('cpn_components_workspace_bytes', c_int64, [c_int32, c_int32, c_int32]),
     ('cpn_components_label', ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                             c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    ('cpn_conv_train_pack', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_conv_wgrad_workspace_bytes', c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    ('cpn_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                      c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    ('cpn_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -48,6 +48,8 @@ SOURCES = {
     # the training objective shares the decode's float32 arithmetic (decode_device.h) and defines its float64 sums and gradients
     # by their order of operations: no FMA contraction
     'cpn_objective.hip': ['-ffp-contract=off'],
+    # trainable convolution: weight packing on the device and the MFMA weight gradient (slab partition: csrc/wgrad_slabs.h)
+    'conv_train.hip': [],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -56,7 +58,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

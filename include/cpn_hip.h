@@ -974,6 +974,50 @@ int cpn_components_label(const int32_t *in, int64_t pixel_stride, int64_t channe
                          int32_t connectivity, int32_t mode, int32_t first, int32_t *out, int64_t out_pixel_stride,
                          int64_t out_channel_stride, int32_t *counts, void *workspace, void *stream);
 
+/* ---- Trainable convolution ---------------------------------------------------------------------------------
+ * What celldetection_amd.nn.conv2d needs besides cpn_conv2d to train a dense stride-1 convolution (csrc/conv_train.hip,
+ * csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * The rule.  Supported: groups 1, stride 1, dilation 1, a square odd kernel k in {1, 3, 5, 7}, zero padding k / 2, cin and cout
+ * positive multiples of 32.  Activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32,
+ * the forward output and the input gradient are stored as bf16, the weight and bias gradients are fp32 sums rounded once to
+ * the dtype asked for.  Activations are NHWC bf16 with the channel count as pixel stride: x [N][H][W][cin], y and dy
+ * [N][H][W][cout].  dtype codes: 0 = fp32, 1 = bf16.
+ *
+ * Forward and input gradient are calls of cpn_conv2d (act none, one plain source, dst_stride = channels) on weights packed on the
+ * device by cpn_conv_train_pack from w [cout][cin][k][k], in the layout of cpn_op_desc.weight_offset:
+ *   CPN_CONV_PACK_FORWARD  [(cin / 32) * k * k items (+ one zero item when odd)][cout][32]: item (chunk, ky * k + kx), output
+ *                          channel co, lane c = w[co][32 * chunk + c][ky][kx]; cin_b = cin, cout_b = cout, with the bias.
+ *   CPN_CONV_PACK_DGRAD    [(cout / 32) * k * k items (+ one zero item when odd)][cin][32]: item (chunk, ky * k + kx), output
+ *                          channel ci, lane c = w[32 * chunk + c][ci][k - 1 - ky][k - 1 - kx]: the taps flipped, the channel
+ *                          roles swapped; cin_b = cout, cout_b = cin, no bias.  With stride 1 and padding k / 2 this conv of dy
+ *                          IS the input gradient: dx[n][y][x][ci] = sum dy[n][y + ky - p][x + kx - p][co] * w[co][ci][k-1-ky][k-1-kx].
+ *
+ * Weight gradient: dw[co][ci][ky][kx] = sum over n, y, x of dy[n][y][x][co] * x[n][y + ky - p][x + kx - p][ci], p = k / 2, zeros
+ * outside the image; bias gradient: db[co] = sum over n, y, x of dy[n][y][x][co].  The pixel range is split into slabs of
+ * slab_rows consecutive image rows (of the N * H rows of the batch; the last slab may be partial, a slab may cross from one image
+ * into the next; slab_rows 0 = chosen by the library).  Within a slab the pixels are reduced in ascending order, 16 per step of
+ * the bf16 MFMA (v_mfma_f32_32x32x16_bf16) into one fp32 accumulator per element; the slabs' partial sums are written to the
+ * workspace and added by a second kernel in ascending slab order.  No floating-point atomics: the result is bit-identical from
+ * run to run.  Length of the fp32 chain of one dw element: MFMA steps per slab (= ceil(slab_rows * W / 16)) + 2 for the
+ * MFMA-internal sum + one add per slab.  The bias gradient sums a slab in eight interleaved chains per channel (pixel index mod 8,
+ * ascending), adds the eight in order, then the slabs in ascending order: ceil(slab_rows * W / 8) + 8 + slabs.
+ * cpn_conv_wgrad_info answers without touching the device, and rejects what the launch rejects:
+ *   info = {slabs, slab_rows, MFMA steps per slab, reduce chain (adds of the second kernel), chain of a bias element}.
+ * dw ([cout][cin][k][k]) or db ([cout]) may be NULL: that gradient is not computed.  workspace:
+ * cpn_conv_wgrad_workspace_bytes(...) bytes on the device for the same arguments (0 for arguments the call rejects).
+ * N * H * W and cin * cout * k * k <= 2^31 - 1 (CPN_E_UNSUPPORTED above).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_CONV_PACK_FORWARD 0
+#define CPN_CONV_PACK_DGRAD 1
+int cpn_conv_train_pack(const void *w, int32_t w_dtype, int32_t cout, int32_t cin, int32_t k, int32_t mode, void *packed,
+                        void *stream);
+int64_t cpn_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t k, int32_t slab_rows);
+int cpn_conv_wgrad(const void *x, const void *dy, int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t k,
+                   int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db, int32_t db_dtype, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+int cpn_conv_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t k, int32_t slab_rows, int32_t info[5]);
+
 #ifdef __cplusplus
 }
 #endif
