@@ -241,6 +241,19 @@ _SIGNATURES = [
     ('cpn_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                       c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     ('cpn_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    ('cpn_bn_info', ctypes.c_int, [c_int64, c_int64, c_int64, POINTER(c_int64)]),
+    ('cpn_bn_workspace_bytes', c_int64, [c_int64, c_int64, c_int64]),
+    ('cpn_bn_train_stats', ctypes.c_int, [c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                          c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int64, c_void_p]),
+    ('cpn_bn_eval_coeffs', ctypes.c_int, [c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_double,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ('cpn_bn_apply', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    ('cpn_bn_backward_reduce', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
+                                              c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                              c_void_p, c_int64, c_void_p]),
+    ('cpn_bn_backward_input', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -50,6 +50,9 @@ SOURCES = {
     'cpn_objective.hip': ['-ffp-contract=off'],
     # trainable convolution: weight packing on the device and the MFMA weight gradient (slab partition: csrc/wgrad_slabs.h)
     'conv_train.hip': [],
+    # trainable batch normalisation (+ ReLU): fp64 sums in a fixed order and named fp32 fmas (lane mapping: csrc/bn_slabs.h): no
+    # FMA contraction
+    'batch_norm.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -58,7 +61,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'bn_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -1018,6 +1018,76 @@ int cpn_conv_wgrad(const void *x, const void *dy, int32_t N, int32_t H, int32_t 
                    int64_t workspace_bytes, void *stream);
 int cpn_conv_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t k, int32_t slab_rows, int32_t info[5]);
 
+/* ---- Trainable batch normalisation --------------------------------------------------------------------------
+ * What celldetection_amd.nn.batch_norm runs: BatchNorm2d with an optional fused ReLU, forward and gradients
+ * (csrc/batch_norm.hip, csrc/bn_slabs.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * Layout.  x, y, dy and dx are [M][C]: M = N * H * W pixels of C channels, element (p, c) at p * C + c (a channels-last
+ * [N, C, H, W] tensor), all four of one dtype, fp32 or bf16.  C is a positive multiple of 8; 1 <= M <= 2^31 - 1 (CPN_E_UNSUPPORTED
+ * above); element indices are 64-bit.  dtype codes: 0 = fp32, 1 = bf16.  weight (gamma), bias (beta), the running buffers, dgamma
+ * and dbeta are [C] of the dtype passed with them; weight and bias may be NULL (1 and 0).  save_mean, save_invstd, scale and
+ * shift are [C] fp32.  x, y, dy, dx and the workspace are read and written 16 bytes at a time: each must start at a 16-byte
+ * aligned address (CPN_E_INVALID otherwise; rows are multiples of 16 bytes because C is a multiple of 8).
+ *
+ * Partition.  A pixel is V = C / 8 vectors of 8 channels; the vectors are cut into channel blocks of at most 256.  A workgroup of
+ * 256 lanes owns one block of vb vectors and one slab of slab_pixels consecutive pixels (the last slab may be partial;
+ * slab_pixels 0 = chosen by the library, a value above M means M; a slab_pixels that gives more than 2^24 - 1 slabs, the most
+ * workgroups of one launch, is CPN_E_UNSUPPORTED; the library's own choice never gives more than 2048), and moves R = floor(256 / vb) consecutive pixels per step:
+ * lane l holds vector l % vb of pixel l / vb of the step, lanes >= R * vb idle.  cpn_bn_info answers without touching the device
+ * and rejects what every launch rejects:
+ *   info = {slabs, slab_pixels, R of the first block, channel blocks, chain of a channel sum}.
+ *
+ * Sums.  Every sum over pixels is an fp64 sum of terms that are exact in fp64 (x, x * x, g, g * x of fp32 or bf16 values), in a
+ * fixed order: a lane adds its own pixels in ascending order, the min(R, slab pixels) lane partials of a channel are added in
+ * ascending lane order, the slabs' results go to the workspace [slab][C][2] and are added in ascending slab order.  No
+ * floating-point atomics: the result is bit-identical from run to run.  Chain of a channel sum: ceil(slab_pixels / R) + min(R,
+ * slab_pixels) + slabs, never more than M + 1 + slabs; info reports the longest over the channel blocks + 6 for the fp64
+ * operations of the finalising formulas below.
+ *
+ * cpn_bn_train_stats, from sum x and sum x^2, in fp64:
+ *   mean = sum x / M;  var = max(sum x^2 / M - mean * mean, 0);  invstd = 1 / sqrt(var + eps);
+ *   scale = gamma * invstd;  shift = beta - mean * scale,
+ * save_mean = mean, save_invstd = invstd, scale and shift each rounded once to fp32.  Where a running buffer is given it is
+ * updated by the same kernel, in fp64, rounded once to its dtype:
+ *   running_mean = (1 - momentum) * running_mean + momentum * mean
+ *   running_var  = (1 - momentum) * running_var + momentum * var * M / (M - 1)      (M = 1 with running_var: CPN_E_INVALID).
+ * cpn_bn_eval_coeffs: mean = running_mean, invstd = 1 / sqrt(running_var + eps), scale and shift as above, in fp64, each rounded
+ * once to fp32 into the same four vectors.
+ *
+ * cpn_bn_apply: t = fmaf(x, scale, shift) in fp32 with x widened exactly; y = t, or for relu != 0: t > 0 ? t : 0; a bf16 y is
+ * rounded to nearest even.
+ *
+ * Backward: g = dy, or for relu != 0: dy where fmaf(x, scale, shift) > 0 and 0 elsewhere -- the mask is recomputed from x, scale
+ * and shift by the same single fma, so it is the forward's mask bit for bit and the gradient at t == 0 is 0.  y is not read.
+ * cpn_bn_backward_reduce, from sum g and sum g x, with mean = save_mean and invstd = save_invstd widened to fp64:
+ *   dbeta = sum g;  dgamma = invstd * (sum g x - mean * sum g), each rounded once to its dtype (either may be NULL);
+ *   coeffs (NULL or [3][C] fp32), in fp64 with the unrounded dgamma, each rounded once to fp32:
+ *     a = gamma * invstd;  b = -a * invstd * dgamma / M;  c = -a * sum g / M - b * mean.
+ * cpn_bn_backward_input: dx = fmaf(a, g, fmaf(b, x, c)) in fp32, rounded to the dtype of x (training: a, b, c = the three rows of
+ * coeffs); with b = c = NULL dx = fmaf(a, g, 0) (eval: a = scale).
+ *
+ * workspace: cpn_bn_workspace_bytes(M, C, slab_pixels) bytes on the device (slabs * C * 2 fp64; 0 for arguments the call
+ * rejects); a smaller one is CPN_E_WORKSPACE.  Every launch validates before it touches a pointer.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_bn_info(int64_t M, int64_t C, int64_t slab_pixels /* 0 = auto */, int64_t info[5]);
+int64_t cpn_bn_workspace_bytes(int64_t M, int64_t C, int64_t slab_pixels);
+int cpn_bn_train_stats(const void *x, int32_t x_dtype, int64_t M, int64_t C, int64_t slab_pixels, const void *weight,
+                       int32_t weight_dtype, const void *bias, int32_t bias_dtype, void *running_mean, void *running_var,
+                       int32_t running_dtype, double momentum, double eps, float *save_mean, float *save_invstd, float *scale,
+                       float *shift, void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_bn_eval_coeffs(int64_t C, const void *weight, int32_t weight_dtype, const void *bias, int32_t bias_dtype,
+                       const void *running_mean, const void *running_var, int32_t running_dtype, double eps, float *save_mean,
+                       float *save_invstd, float *scale, float *shift, void *stream);
+int cpn_bn_apply(const void *x, void *y, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels, const float *scale,
+                 const float *shift, int32_t relu, void *stream);
+int cpn_bn_backward_reduce(const void *x, const void *dy, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels,
+                           const float *scale, const float *shift, int32_t relu, const float *save_mean, const float *save_invstd,
+                           const void *weight, int32_t weight_dtype, void *dgamma, int32_t dgamma_dtype, void *dbeta,
+                           int32_t dbeta_dtype, float *coeffs, void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_bn_backward_input(const void *x, const void *dy, void *dx, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels,
+                          const float *scale, const float *shift, int32_t relu, const float *a, const float *b, const float *c,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
