@@ -254,6 +254,13 @@ _SIGNATURES = [
                                               c_void_p, c_int64, c_void_p]),
     ('cpn_bn_backward_input', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ('cpn_tail_info', ctypes.c_int, [c_int64, c_int64, c_int32, c_int32, c_int64, POINTER(c_int64)]),
+    ('cpn_tail_workspace_bytes', c_int64, [c_int64, c_int64, c_int32, c_int32, c_int64]),
+    ('cpn_tail_forward', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_float, c_int64, c_int64, c_int32,
+                                        c_int32, c_void_p, c_int32, c_void_p]),
+    ('cpn_tail_backward', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_float, c_int64, c_int64, c_int32,
+                                         c_int32, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
+                                         c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -53,6 +53,8 @@ SOURCES = {
     # trainable batch normalisation (+ ReLU): fp64 sums in a fixed order and named fp32 fmas (lane mapping: csrc/bn_slabs.h): no
     # FMA contraction
     'batch_norm.hip': ['-ffp-contract=off'],
+    # trainable ReadOut tail: Dropout2d + 1x1 conv to few channels, three MFMA products (partition: csrc/tail_slabs.h)
+    'readout_tail.hip': [],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -61,7 +63,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'bn_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

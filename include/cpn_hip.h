@@ -1088,6 +1088,58 @@ int cpn_bn_backward_input(const void *x, const void *dy, void *dx, int32_t dtype
                           const float *scale, const float *shift, int32_t relu, const float *a, const float *b, const float *c,
                           void *stream);
 
+/* ---- Trainable ReadOut tail ---------------------------------------------------------------------------------
+ * What celldetection_amd.nn.dropout_conv1x1 runs: Dropout2d fused into a 1x1 convolution to at most 32 output channels, forward
+ * and gradients (csrc/readout_tail.hip, csrc/tail_slabs.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * Layout.  x and dx are [N][HW][cin] bf16 (a channels-last [N, cin, H, W] tensor, HW = H * W), cin a positive multiple of 32, at
+ * most 1024.  weight and dw are [cout][cin], bias and db [cout], 1 <= cout <= 32, each of the dtype passed with it (0 = fp32,
+ * 1 = bf16).  y and dy are [N][cout][HW] planes (a contiguous NCHW tensor), fp32 or bf16.  keep is [N][cin] bytes, non-zero = the
+ * channel of that image is kept (m = 1), or NULL: everything kept.  scale is s = 1 / (1 - p), the fp32 value nearest to it (1 when
+ * nothing is dropped, 0 for p = 1); it must be finite and not negative.  N * HW <= 2^31 - 1 (CPN_E_UNSUPPORTED above).  x, dx and
+ * the workspace are read and written 16 bytes at a time: each must start at a 16-byte aligned address; y and dy at a multiple of
+ * their element size (CPN_E_INVALID otherwise).
+ *
+ * Forward.  acc[n][q][o] = sum over c of m[n][c] * bf16(W[o][c]) * x[n][q][c], an fp32 sum on the bf16 MFMA
+ * (v_mfma_f32_32x32x16_bf16, 16 channels per step in ascending order): the weight operand is masked per image, so a dropped
+ * channel contributes an exact zero and x * s is never rounded.  y = fmaf(acc, s, bias) is rounded once to the dtype of y (bias
+ * widened exactly, 0 without one).  Chain of acc: cin / 16 + 2 (the MFMA-internal sum).  The pixels of an image are cut into tiles
+ * of 32; a tile never holds pixels of two images.
+ *
+ * Backward.  Every use of dy reads its bf16 rounding (round to nearest even), converted inside the kernel from the fp32 or bf16
+ * planes.
+ *   dx[n][q][c] = m[n][c] * s * sum over o of bf16(W[o][c]) * bf16(dy[n][o][q]): an fp32 sum on the MFMA (K = cout padded to 16 or
+ *   32: one or two steps), one multiply by s, rounded once to bf16; exactly 0 for a dropped channel.
+ *   dw[o][c] = s * sum over n of m[n][c] * sum over q of bf16(dy[n][o][q]) * x[n][q][c];  db[o] = sum of bf16(dy[n][o][q]).
+ * Pixels are reduced on the MFMA in slabs that never cross an image: image n is cut into ceil(HW / slab_pixels) slabs of
+ * slab_pixels consecutive pixels (the last may be partial; slab_pixels 0 = chosen by the library, a value above HW means HW; more
+ * than 2^24 - 1 slabs is CPN_E_UNSUPPORTED).  Within a slab the pixels are reduced in ascending order, 16 per MFMA step, into one
+ * fp32 accumulator per element; a slab's fp32 partial goes to the workspace, and a second kernel adds the slabs in ascending
+ * (n, slab) order, skipping the slabs of the images whose channel was dropped (a multiplication by 0 or 1, exact), multiplies by
+ * s once and rounds once to the dtype of dw.  Chain of a dw element: MFMA steps per slab (= ceil(slab_pixels / 16)) + 2 for the
+ * MFMA-internal sum + the reduce chain (one add per slab + the multiplication by s).  The bias gradient sums a slab in eight
+ * interleaved chains per channel (pixel index inside the slab mod 8, ascending), adds the eight in order, then the slabs in
+ * ascending order: ceil(slab_pixels / 8) + 8 + slabs; it is neither masked nor scaled.  No floating-point atomics: the result is
+ * bit-identical from run to run.  Rows cout ... 31 of the MFMA tile read zeros and are never written: nothing behind weight, bias,
+ * dy, y, dw or db is touched.
+ *
+ * cpn_tail_info answers without touching the device and rejects what the launches reject:
+ *   info = {slabs, slab_pixels, MFMA steps per slab, reduce chain, chain of a bias element, forward chain, slabs per image,
+ *           MFMA steps of a dx element}.
+ * cpn_tail_backward: dx, dw and db may each be NULL: that gradient is not computed, and what only it reads is not read (x for dw,
+ * weight for dx).  workspace: cpn_tail_workspace_bytes(...) bytes on the device for the same arguments (slabs * (cin * cout +
+ * cout) fp32; 0 for arguments the call rejects), needed for dw or db; a smaller one is CPN_E_WORKSPACE.  Every launch validates
+ * before it touches a pointer.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_tail_info(int64_t N, int64_t HW, int32_t cin, int32_t cout, int64_t slab_pixels /* 0 = auto */, int64_t info[8]);
+int64_t cpn_tail_workspace_bytes(int64_t N, int64_t HW, int32_t cin, int32_t cout, int64_t slab_pixels);
+int cpn_tail_forward(const void *x, const void *weight, int32_t weight_dtype, const void *bias, int32_t bias_dtype,
+                     const uint8_t *keep, float scale, int64_t N, int64_t HW, int32_t cin, int32_t cout, void *y, int32_t y_dtype,
+                     void *stream);
+int cpn_tail_backward(const void *x, const void *dy, int32_t dy_dtype, const void *weight, int32_t weight_dtype, const uint8_t *keep,
+                      float scale, int64_t N, int64_t HW, int32_t cin, int32_t cout, int64_t slab_pixels, void *dx, void *dw,
+                      int32_t dw_dtype, void *db, int32_t db_dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
