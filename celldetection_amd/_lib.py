@@ -261,6 +261,12 @@ _SIGNATURES = [
     ('cpn_tail_backward', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_float, c_int64, c_int64, c_int32,
                                          c_int32, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
                                          c_void_p]),
+    ('cpn_grouped_conv_pack', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_grouped_conv_dilate', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_grouped_conv_wgrad_workspace_bytes', c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    ('cpn_grouped_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    ('cpn_grouped_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

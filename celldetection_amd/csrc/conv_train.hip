@@ -25,6 +25,7 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "wgrad_bias.h"  // ct_bias_slab_kernel / ct_bias_reduce_kernel, ct_bf16_rne, the dtype codes
 #include "wgrad_slabs.h"
 
 namespace {
@@ -37,14 +38,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int CT_CH = 128;   // pixels per staged chunk (8 MFMA steps)
 constexpr int CT_ROW = 64;   // bytes of an LDS row: 32 channels
-constexpr int CT_F32 = 0, CT_BF16 = 1;
-
-__device__ __forceinline__ uint16_t ct_bf16_rne(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t) ((u >> 16) | 0x40);  // NaN stays NaN
-    return (uint16_t) ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float ct_bf16_value(uint16_t b) { return __uint_as_float((uint32_t) b << 16); }
 
 __global__ __launch_bounds__(256) void ct_pack_kernel(const void *w, int w_dtype, int Cout, int Cin, int K, int dgrad,
                                                        uint16_t *packed, long total) {
@@ -196,33 +189,6 @@ __global__ __launch_bounds__(256) void ct_wgrad_reduce_kernel(const float *__res
     const long o = cc * KK + e / ((long) Cout * Cin);
     if (dw_dtype == CT_BF16) ((uint16_t *) dw)[o] = ct_bf16_rne(sum);
     else ((float *) dw)[o] = sum;
-}
-
-__global__ __launch_bounds__(256) void ct_bias_slab_kernel(const uint16_t *__restrict__ dy, float *__restrict__ wsb, WgSlabs part,
-                                                            int Cout) {
-    __shared__ float part_sum[WGS_BIAS_LANES][32];
-    const int c = threadIdx.x & 31, chain = threadIdx.x >> 5, ch = blockIdx.y * 32 + c;
-    int64_t p0, p1;
-    wgs_range(part, blockIdx.x, &p0, &p1);
-    float acc = 0.f;
-    for (int64_t p = p0 + chain; p < p1; p += WGS_BIAS_LANES) acc += ct_bf16_value(dy[p * Cout + ch]);
-    part_sum[chain][c] = acc;
-    __syncthreads();
-    if (chain == 0) {
-        float s = part_sum[0][c];
-        for (int i = 1; i < WGS_BIAS_LANES; ++i) s += part_sum[i][c];
-        wsb[(int64_t) blockIdx.x * Cout + ch] = s;
-    }
-}
-
-__global__ __launch_bounds__(256) void ct_bias_reduce_kernel(const float *__restrict__ wsb, int slabs, int Cout, void *db,
-                                                              int db_dtype) {
-    const int ch = blockIdx.x * 256 + threadIdx.x;
-    if (ch >= Cout) return;
-    float sum = wsb[ch];
-    for (int s = 1; s < slabs; ++s) sum += wsb[(int64_t) s * Cout + ch];
-    if (db_dtype == CT_BF16) ((uint16_t *) db)[ch] = ct_bf16_rne(sum);
-    else ((float *) db)[ch] = sum;
 }
 
 // The kernel per filter size: MT fragments of 32 output channels per wave (a workgroup: 64 MT output x 64 input channels), and the

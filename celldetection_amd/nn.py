@@ -15,9 +15,10 @@ include/cpn_hip.h):
 
 Supported: ``groups = 1``, ``stride = 1``, ``dilation = 1``, a square odd ``k`` in {1, 3, 5, 7}, ``padding = k // 2`` with zeros,
 ``Cin`` and ``Cout`` multiples of 32, a 4-D input on the GPU.  Everything else raises ``NotImplementedError`` naming the argument;
-there is no CPU fallback.  Known limit: the strided or grouped encoder convs of the reference model stay stock torch operations
-(``convert_conv2d_`` leaves them and says why); it also leaves the final 1x1 convs of the heads (1 / 2 / 20 output channels), which
-are the business of ``dropout_conv1x1`` below.
+there is no CPU fallback.  ``convert_conv2d_`` leaves every other conv and says why: the grouped 3x3 convs of the encoder are the
+business of ``grouped_conv2d``, the final 1x1 convs of the heads (1 / 2 / 20 output channels) of ``dropout_conv1x1``, both below.
+Known limit: the stem, the max-pool, the strided 1x1 shortcuts and the residual add of the encoder, and the nearest resize with
+concat in the decoder, stay stock torch operations.
 
 Arithmetic: activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32, the forward output
 and the input gradient are stored as bf16, the weight and bias gradients are fp32 sums rounded once to the parameter's dtype.  ``x``
@@ -33,7 +34,12 @@ The tail of a ReadOut head, ``Dropout2d -> Conv 1x1`` to 1 / 2 / 20 channels, ru
 ``torch.autograd.Function``: three passes over the head's largest activation instead of stock's seven, and only ``x`` saved), the
 ``nn.Conv2d`` drop-in ``DropoutConv1x1`` and ``convert_readout_tail_`` (third part of this module; the rule is the "Trainable
 ReadOut tail" section of include/cpn_hip.h).  After the three converts a ReadOut head runs conv -> norm -> ReLU -> dropout -> 1x1
-without leaving the library; the bilinear resize behind the heads and the encoder stay stock.
+without leaving the library; the bilinear resize behind the heads stays stock.
+
+The grouped 3x3 ``conv2`` of the ResNeXt encoder's bottleneck blocks, at stride 1 and 2, runs here as well: ``grouped_conv2d`` (one
+``torch.autograd.Function``), the ``nn.Conv2d`` drop-in ``GroupedConv2d`` and ``convert_grouped_conv2d_`` (fourth part of this
+module; the rule is the "Trainable grouped convolution" section of include/cpn_hip.h).  The 1x1 ``conv1`` / ``conv3`` around it are
+dense stride-1 convs that ``convert_conv2d_`` takes.
 """
 import ctypes
 
@@ -44,7 +50,9 @@ from .ops import _need_cuda
 
 __all__ = ['conv2d', 'Conv2d', 'convert_conv2d_', 'is_supported', 'pack_weight', 'conv2d_weight_grad', 'weight_grad_info',
            'batch_norm', 'batch_norm_forward', 'batch_norm_info', 'BatchNorm2d', 'convert_batchnorm2d_',
-           'dropout_conv1x1', 'dropout_conv1x1_backward', 'readout_tail_info', 'DropoutConv1x1', 'convert_readout_tail_']
+           'dropout_conv1x1', 'dropout_conv1x1_backward', 'readout_tail_info', 'DropoutConv1x1', 'convert_readout_tail_',
+           'grouped_conv2d', 'GroupedConv2d', 'convert_grouped_conv2d_', 'grouped_weight_grad_info', 'grouped_conv2d_weight_grad',
+           'grouped_pack_weight', 'grouped_dilate']
 
 KERNEL_SIZES = (1, 3, 5, 7)
 _DTYPES = {torch.float32: _lib.CONV_TRAIN_F32, torch.bfloat16: _lib.CONV_TRAIN_BF16}
@@ -284,7 +292,7 @@ def convert_conv2d_(module):
     for name, parent in list(module.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f'{name}.{child_name}' if name else child_name
-            if isinstance(child, (Conv2d, DropoutConv1x1)) or not isinstance(child, torch.nn.modules.conv._ConvNd):
+            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d)) or not isinstance(child, torch.nn.modules.conv._ConvNd):
                 continue
             why = _why_not(child) if isinstance(child, torch.nn.Conv2d) else f'{type(child).__name__}: 2-D convs only'
             if why is None:
@@ -801,4 +809,282 @@ def convert_readout_tail_(module):
             replaced.append(full)
             if fuse:
                 setattr(parent, prev[0], torch.nn.Identity())
+    return replaced, left
+
+
+# ---- the grouped 3x3 conv of a ResNeXt bottleneck block ("Trainable grouped convolution" of include/cpn_hip.h,
+# csrc/grouped_conv_train.hip, csrc/grouped_conv.h)
+#
+# ``conv2`` of every block of a ResNeXt encoder: C -> C channels in groups of ``C / groups`` in {4, 8, 16, 32, 64}, 3x3, padding 1,
+# stride 1 or 2.  It runs as ``C / bw`` block-diagonal dense convs ("bundles") of bw = 32 | 64 channels, the geometry of
+# ``pack._bundle_geometry``: forward and input gradient are ``cpn_conv2d`` on records packed on the device every step, the weight
+# gradient computes the diagonal 32 x 32 fragments only.  Stride 2 goes through zero-dilation: ``dZ[2i][2j] = dY[i][j]``, then the
+# stride-1 input and weight gradients of ``dZ`` are those of the strided conv.  Known limit: that does 4 x the minimal work of the
+# three strided convs of an encoder and holds one more tensor of ``x``'s size.  ``groups = 1`` with ``C`` = 32 or 64 is the
+# one-bundle edge of the family and runs through ``grouped_conv2d``; ``GroupedConv2d`` and ``convert_grouped_conv2d_`` take
+# ``groups > 1`` only (dense convs are ``Conv2d``'s).
+
+GROUP_WIDTHS = (4, 8, 16, 32, 64)
+
+
+def _grouped_channels(in_channels, out_channels, groups):
+    """The first channel argument the grouped conv does not run, as a sentence, or None."""
+    if groups < 1 or in_channels % groups or out_channels % groups:
+        return f'groups {groups}: must divide in_channels {in_channels} and out_channels {out_channels}'
+    if in_channels != out_channels:
+        return f'out_channels {out_channels}: the grouped conv needs out_channels == in_channels ({in_channels})'
+    cig = in_channels // groups
+    if cig not in GROUP_WIDTHS:
+        return f'groups {groups}: in_channels / groups = {cig}, the grouped conv runs {GROUP_WIDTHS} channels per group only'
+    bw = 64 if cig == 64 else 32
+    if in_channels < bw or in_channels % bw:
+        return f'in_channels {in_channels}: the grouped conv needs a positive multiple of {bw} for {cig} channels per group'
+    return None
+
+
+def _grouped_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels, transposed=False):
+    """The first argument ``GroupedConv2d`` does not run, as a sentence, or None."""
+    if transposed:
+        return 'transposed convs are not run'
+    if groups <= 1:
+        return f'groups {groups}: grouped convs only (groups > 1)'
+    if _pair(kernel_size) != (3, 3):
+        return f'kernel_size {kernel_size}: 3x3 only'
+    if _pair(stride) not in ((1, 1), (2, 2)):
+        return f'stride {stride}: stride 1 or 2 only'
+    if _pair(dilation) != (1, 1):
+        return f'dilation {dilation}: dilation 1 only'
+    if padding != 'same' and (isinstance(padding, str) or _pair(padding) != (1, 1)):
+        return f'padding {padding!r}: 1 zero on every side only'
+    if padding == 'same' and _pair(stride) != (1, 1):
+        return f"padding 'same': stride 1 only"
+    if padding_mode != 'zeros':
+        return f"padding_mode '{padding_mode}': zeros only"
+    return _grouped_channels(in_channels, out_channels, groups)
+
+
+def _check_grouped(weight, stride, groups):
+    """Raises NotImplementedError naming the argument the kernels do not run -> (C, channels per group, stride)."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise NotImplementedError(f'kernel_size / weight {tuple(weight.shape)}: the grouped conv runs [C, C / groups, 3, 3] weights only')
+    if weight.dtype not in _DTYPES:
+        raise NotImplementedError(f'weight dtype {weight.dtype}: the grouped conv takes float32 or bfloat16 parameters')
+    c = int(weight.shape[0])
+    cig, stride = _grouped_args(int(weight.shape[1]) * groups if isinstance(groups, int) else 0, c, stride, groups)
+    return c, cig, stride
+
+
+def _grouped_args(in_channels, out_channels, stride, groups):
+    """Raises NotImplementedError naming the argument the kernels do not run -> (channels per group, stride)."""
+    if not isinstance(groups, int) or groups < 1:
+        raise NotImplementedError(f'groups {groups!r}: a positive int')
+    if _pair(stride) not in ((1, 1), (2, 2)):
+        raise NotImplementedError(f'stride {stride}: the grouped conv runs stride 1 or 2 only')
+    why = _grouped_channels(in_channels, out_channels, groups)
+    if why is not None:
+        raise NotImplementedError(why)
+    return in_channels // groups, _pair(stride)[0]
+
+
+def _grouped_desc(c, cig, stride, bias):
+    """cpn_op_desc of the grouped conv as C / bw block-diagonal dense convs of bw -> bw channels (pack._bundle_geometry)."""
+    bw = 64 if cig == 64 else 32
+    d = _conv_desc(bw, bw, 3, bias)
+    d.c0_used, d.cout_real, d.bundles, d.stride = c, c, c // bw, stride
+    return d
+
+
+def grouped_pack_weight(weight, groups, mode='forward'):
+    """weight [C, C / groups, 3, 3] (float32 | bfloat16, on the GPU) -> the bf16 records ``cpn_conv2d`` reads for the C / bw
+    block-diagonal convs, packed on the device: [bundle, (bw / 32) 9 items (+ one zero item when odd), bw, 32]; ``'dgrad'``: the taps
+    flipped and the channel roles swapped inside each group.  Entries across two groups of a bundle are exact zeros."""
+    _need_cuda(weight)
+    c, cig, _ = _check_grouped(weight, 1, groups)
+    w = weight.detach().contiguous()
+    bw = 64 if cig == 64 else 32
+    items = bw // 32 * 9
+    packed = torch.empty((c // bw, items + items % 2, bw, 32), dtype=torch.bfloat16, device=w.device)
+    _lib.check(_lib.load().cpn_grouped_conv_pack(_lib.ptr(w), _DTYPES[w.dtype], c, cig, _lib.CONV_PACK_MODES[mode], _lib.ptr(packed),
+                                                 _lib.stream_ptr()), 'grouped_conv_pack')
+    return packed
+
+
+def _run_grouped(src, packed, bias, c, cig, stride):
+    """cpn_conv2d on a bf16 tensor whose memory is NHWC -> bf16 [N, C, Hout, Wout] in channels_last."""
+    n, _, h, w = src.shape
+    out = torch.empty((n, c, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=torch.bfloat16, device=src.device,
+                      memory_format=torch.channels_last)
+    if out.numel() == 0:
+        return out
+    d = _grouped_desc(c, cig, stride, bias is not None)
+    _lib.check(_lib.load().cpn_conv2d(ctypes.byref(d), _lib.ptr(src), c, _lib.ptr(None), 0, _lib.ptr(None), 0, _lib.ptr(out), c,
+                                      n, h, w, _lib.ptr(packed), _lib.ptr(bias), _lib.stream_ptr()), 'grouped_conv2d')
+    return out
+
+
+def grouped_dilate(grad_output, size):
+    """The stride-2 gradient at the input's size: grad_output [N, C, Hout, Wout] -> bf16 dZ [N, C, H, W] in ``torch.channels_last``
+    with ``dZ[..., 2i, 2j] = grad_output[..., i, j]`` and exact zeros elsewhere; ``size`` = (H, W) with Hout = (H - 1) // 2 + 1."""
+    _need_cuda(grad_output)
+    h, w = (int(v) for v in size)
+    n, c, ho, wo = (int(v) for v in grad_output.shape)
+    if c < 32 or c % 32:
+        raise NotImplementedError(f'grad_output of {c} channels: the grouped conv needs a positive multiple of 32')
+    if h < 1 or w < 1 or (ho, wo) != ((h - 1) // 2 + 1, (w - 1) // 2 + 1):
+        raise ValueError(f'grad_output {ho} x {wo} is not the stride-2 output of a {h} x {w} input')
+    gs = _nhwc(grad_output, torch.bfloat16)
+    dz = torch.empty((n, c, h, w), dtype=torch.bfloat16, device=gs.device, memory_format=torch.channels_last)
+    if dz.numel():
+        _lib.check(_lib.load().cpn_grouped_conv_dilate(_lib.ptr(gs), n, h, w, c, _lib.ptr(dz), _lib.stream_ptr()), 'grouped_conv_dilate')
+    return dz
+
+
+def grouped_weight_grad_info(n, h, w, channels, groups, stride=1, slab_rows=0):
+    """What ``grouped_conv2d_weight_grad`` would run on ``n`` inputs of ``h`` x ``w`` -> dict(slabs, slab_rows, steps (MFMA steps per
+    slab), reduce_chain, bias_chain).  Host arithmetic only: needs no GPU.  Raises like the launch for a call it rejects."""
+    info = (ctypes.c_int32 * 5)()
+    cig = channels // groups if groups > 0 and channels % groups == 0 else 0
+    _lib.check(_lib.load().cpn_grouped_conv_wgrad_info(n, h, w, channels, cig, stride, slab_rows, info), 'grouped_conv_wgrad_info')
+    return dict(zip(('slabs', 'slab_rows', 'steps', 'reduce_chain', 'bias_chain'), (int(v) for v in info)))
+
+
+def grouped_conv2d_weight_grad(x, grad_output, groups, stride=1, slab_rows=0, weight=True, bias=True, dtype=torch.float32,
+                               bias_dtype=None, dilated=None):
+    """(x [N, C, H, W], grad_output [N, C, Hout, Wout]) -> (dW [C, C / groups, 3, 3] | None, db [C] | None): the gradients
+    ``grouped_conv2d`` returns for its weight and bias, as fp32 sums over the bf16-rounded operands rounded once to ``dtype`` /
+    ``bias_dtype``.  ``slab_rows``: image rows per slab of the reduction (0: chosen by the library); ``dilated``: stride 2, the
+    result of ``grouped_dilate(grad_output, (H, W))`` when the caller has it already."""
+    _need_cuda(x, grad_output)
+    n, c, h, w = (int(v) for v in x.shape)
+    bias_dtype = dtype if bias_dtype is None else bias_dtype
+    if dtype not in _DTYPES or bias_dtype not in _DTYPES:
+        raise NotImplementedError(f'dtype {dtype} / {bias_dtype}: gradients are float32 or bfloat16')
+    cig, stride = _grouped_args(c, int(grad_output.shape[1]), stride, groups)
+    want = (n, c, (h - 1) // stride + 1, (w - 1) // stride + 1)
+    assert tuple(grad_output.shape) == want, (tuple(grad_output.shape), want)
+    dw = torch.zeros((c, cig, 3, 3), dtype=dtype, device=x.device) if weight else None
+    db = torch.zeros((c,), dtype=bias_dtype, device=x.device) if bias else None
+    if n * h * w == 0 or not (weight or bias):
+        return dw, db
+    xs, gs = _nhwc(x, torch.bfloat16), _nhwc(grad_output, torch.bfloat16)
+    dz = gs
+    if stride == 2 and weight:
+        dz = grouped_dilate(gs, (h, w)) if dilated is None else dilated
+    lib = _lib.load()
+    nbytes = int(lib.cpn_grouped_conv_wgrad_workspace_bytes(n, h, w, c, cig, stride, slab_rows))
+    if nbytes <= 0:
+        _lib.check(lib.cpn_grouped_conv_wgrad_info(n, h, w, c, cig, stride, slab_rows, (ctypes.c_int32 * 5)()), 'grouped_conv_wgrad')
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.cpn_grouped_conv_wgrad(_lib.ptr(xs), _lib.ptr(dz), _lib.ptr(gs), n, h, w, c, cig, stride, slab_rows, _lib.ptr(dw),
+                                          _DTYPES[dtype], _lib.ptr(db), _DTYPES[bias_dtype], _lib.ptr(ws), nbytes, _lib.stream_ptr()),
+               'grouped_conv_wgrad')
+    return dw, db
+
+
+class _GroupedConv2dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, groups):
+        c, cig = int(weight.shape[0]), int(weight.shape[1])
+        xs = _nhwc(x, torch.bfloat16)
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        out = _run_grouped(xs, grouped_pack_weight(weight, groups, 'forward'), b32, c, cig, stride)
+        ctx.save_for_backward(xs, weight)
+        ctx.x_dtype, ctx.stride, ctx.groups = x.dtype, stride, groups
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        xs, weight = ctx.saved_tensors
+        c, cig = int(weight.shape[0]), int(weight.shape[1])
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.bias_dtype is not None
+        gs = _nhwc(grad_output, torch.bfloat16)
+        dz = gs  # the gradient at the input's size: stride 2 by zero-dilation, shared by the input and the weight gradient
+        if ctx.stride == 2 and (need_x or need_w):
+            dz = grouped_dilate(gs, xs.shape[2:])
+        dx = dw = db = None
+        if need_x:  # the stride-1 conv of dz with the flipped, channel-swapped weights
+            dx = _run_grouped(dz, grouped_pack_weight(weight, ctx.groups, 'dgrad'), None, c, cig, 1).to(ctx.x_dtype)
+        if need_w or need_b:
+            dw, db = grouped_conv2d_weight_grad(xs, gs, ctx.groups, ctx.stride, weight=need_w, bias=need_b, dtype=weight.dtype,
+                                                bias_dtype=ctx.bias_dtype or weight.dtype, dilated=dz)
+        return dx, dw, db, None, None
+
+
+def grouped_conv2d(x, weight, bias=None, stride=1, groups=1):
+    """``torch.nn.functional.conv2d(x, weight, bias, stride, padding=1, groups=groups)`` for a 3x3 ``weight`` ``[C, C / groups, 3, 3]``
+    of the supported family (comment above), with gradients for ``x``, ``weight`` and ``bias`` as autograd asks for them -> bf16
+    ``[N, C, (H - 1) // stride + 1, (W - 1) // stride + 1]`` in ``torch.channels_last``.  Anything unsupported raises
+    ``NotImplementedError`` naming the argument; there is no fallback."""
+    if x.dim() != 4:
+        raise NotImplementedError(f'input of {x.dim()} dimensions: the grouped conv takes a 4-D [N, C, H, W] input')
+    c, cig, stride = _check_grouped(weight, stride, groups)
+    if x.dtype not in _DTYPES:
+        raise NotImplementedError(f'input dtype {x.dtype}: the grouped conv takes float32 or bfloat16 activations')
+    if int(x.shape[1]) != c:
+        raise ValueError(f'input has {int(x.shape[1])} channels, weight expects {c}')
+    if bias is not None and (bias.dim() != 1 or int(bias.shape[0]) != c or bias.dtype not in _DTYPES):
+        raise NotImplementedError(f'bias {tuple(bias.shape)} {bias.dtype}: the grouped conv takes a float32 or bfloat16 [{c}] bias')
+    _need_cuda(x, weight, bias)
+    return _GroupedConv2dFunction.apply(x, weight, bias, stride, groups)
+
+
+class GroupedConv2d(torch.nn.Conv2d):
+    """``torch.nn.Conv2d`` with torch's constructor arguments and parameter names (``weight``, ``bias``: ``state_dict``s
+    interchange) whose forward is ``grouped_conv2d``.  ``kernel_size`` is 3 and ``padding`` defaults to 1; an argument outside the
+    supported family raises ``NotImplementedError`` naming it."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=32, bias=True,
+                 padding_mode='zeros', device=None, dtype=None):
+        why = _grouped_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels)
+        if why is not None:
+            raise NotImplementedError(why)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device, dtype)
+
+    def forward(self, x):
+        return grouped_conv2d(x, self.weight, self.bias, self.stride, self.groups)
+
+
+def _grouped_why_not(conv):
+    if type(conv) is not torch.nn.Conv2d:
+        return f'a subclass of torch.nn.Conv2d ({type(conv).__name__}): its forward may differ'
+    if conv.weight.dtype not in _DTYPES:
+        return f'weight dtype {conv.weight.dtype}: float32 or bfloat16 only'
+    return _grouped_unsupported(conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.padding_mode,
+                                conv.in_channels, conv.out_channels, conv.transposed)
+
+
+def _grouped_from_torch(conv):
+    new = GroupedConv2d.__new__(GroupedConv2d)
+    new.__dict__.update(conv.__dict__)  # the same Parameter objects, hooks, training flag and constructor attributes
+    new._parameters = dict(conv._parameters)  # (the registry itself is the new module's own)
+    return new
+
+
+def convert_grouped_conv2d_(module):
+    """Replaces every eligible plain ``torch.nn.Conv2d`` with ``groups > 1`` below ``module`` in place by a ``GroupedConv2d`` that
+    shares its ``Parameter`` objects (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).
+    ``left`` names every other grouped conv with the reason; dense convs are not its business.  ``module`` itself is not replaced
+    when it is such a conv: it is reported as left.  A conv object that sits in several slots is replaced by one object in all of
+    them.  Works before or after the other converts."""
+    replaced, left = [], {}
+    ours = (Conv2d, DropoutConv1x1, GroupedConv2d)
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, ours) and module.groups > 1:
+        left[''] = _grouped_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
+    swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
+    for name, parent in list(module.named_modules()):
+        slots = [(n, c) for n, c in parent._modules.items() if c is not None]  # (named_children() drops repeated objects)
+        for child_name, child in slots:
+            full = f'{name}.{child_name}' if name else child_name
+            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, ours) or child.groups <= 1:
+                continue
+            why = _grouped_why_not(child)
+            if why is not None:
+                left[full] = why
+                continue
+            if id(child) not in swapped:
+                swapped[id(child)] = _grouped_from_torch(child)
+            setattr(parent, child_name, swapped[id(child)])
+            replaced.append(full)
     return replaced, left

@@ -1140,6 +1140,68 @@ int cpn_tail_backward(const void *x, const void *dy, int32_t dy_dtype, const voi
                       float scale, int64_t N, int64_t HW, int32_t cin, int32_t cout, int64_t slab_pixels, void *dx, void *dw,
                       int32_t dw_dtype, void *db, int32_t db_dtype, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Trainable grouped convolution --------------------------------------------------------------------------
+ * What celldetection_amd.nn.grouped_conv2d needs besides cpn_conv2d to train the 3x3 conv2 of a ResNeXt bottleneck block
+ * (csrc/grouped_conv_train.hip, csrc/grouped_conv.h, csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * The rule.  A conv of C -> C channels in groups of cig = C / groups channels, cig in {4, 8, 16, 32, 64}, kernel 3x3, zero padding
+ * 1, dilation 1, stride 1 or 2.  It runs as bundles = C / bw block-diagonal dense convs of bw -> bw channels: bw = 32 for
+ * cig <= 32 (32 / cig groups per bundle), bw = 64 for cig = 64 (one group per bundle); C is a positive multiple of bw.  Arithmetic
+ * and layout are those of the "Trainable convolution" section: bf16 operands (round to nearest even), fp32 accumulation, NHWC bf16
+ * activations with C as pixel stride (x and dx [N][Hin][Win][C]; y and dy [N][Hout][Wout][C], Hout = (Hin - 1) / stride + 1),
+ * dw [C][cig][3][3] and db [C] fp32 sums rounded once to the dtype asked for.  dtype codes: 0 = fp32, 1 = bf16.
+ *
+ * Forward and input gradient are calls of cpn_conv2d (bundles, cin_b = cout_b = bw, c0_used = C, kh = kw = 3, pad 1, act none,
+ * one plain source, dst_stride = C) on weights packed on the device by cpn_grouped_conv_pack from w [C][cig][3][3], in the layout
+ * of cpn_op_desc.weight_offset: [bundle][item = (32-channel chunk of the bundle, tap ky * 3 + kx)][bw][32], (bw / 32) * 9 items
+ * and one zero item behind an odd count IN EVERY BUNDLE (bw = 32: 9 + 1).  With oc the record's output channel and rc = 32 chunk +
+ * lane its reduced channel, both inside the bundle:
+ *   CPN_CONV_PACK_FORWARD  w[bw bundle + oc][rc mod cig][ky][kx] where oc / cig == rc / cig, an exact zero elsewhere; stride 1 or
+ *                          2 in the descriptor, with the bias.
+ *   CPN_CONV_PACK_DGRAD    w[bw bundle + rc][oc mod cig][2 - ky][2 - kx] where oc / cig == rc / cig, an exact zero elsewhere: the
+ *                          taps flipped, the channel roles swapped inside each group; stride 1, no bias.  At stride 1 this conv of
+ *                          dy IS the input gradient.
+ *
+ * Stride 2, by zero-dilation.  cpn_grouped_conv_dilate writes dz [N][Hin][Win][C] with dz[n][2 i][2 j] = dy[n][i][j] and exact
+ * zeros elsewhere (every 16-byte unit of dz written once; 2 (Hout - 1) <= Hin - 1 for even and odd Hin).  The stride-2 output is
+ * y[i][j] = sum w[ky][kx] x[2 i + ky - 1][2 j + kx - 1], so
+ *   dx[u][v] = sum over (i, j, ky, kx) with 2 i + ky - 1 = u, 2 j + kx - 1 = v of dy[i][j] w[ky][kx]
+ *            = sum over ky, kx of dz[u - ky + 1][v - kx + 1] w[ky][kx]: the stride-1 dgrad conv of dz;
+ *   dw[ky][kx] = sum over i, j of dy[i][j] x[2 i + ky - 1][2 j + kx - 1] = sum over all (u, v) of dz[u][v] x[u + ky - 1][v + kx - 1]:
+ *            the stride-1 weight gradient of (x, dz), the odd positions contributing exact zeros.
+ * The bias gradient sums dy itself.  Known limit: 4 x the minimal work and one more tensor of x's size.
+ *
+ * Weight gradient: dw[co][cl][ky][kx] = sum over n, y, x of dz[n][y][x][co] * x[n][y + ky - 1][x + kx - 1][cig (co / cig) + cl]
+ * (stride 1: dz = dy), zeros outside the image.  Only the diagonal 32 x 32 fragments of the (co, ci) matrix are computed: a wave
+ * owns one of them (bw = 32: one bundle; bw = 64: one of the four of a group), a workgroup four of them for one filter row ky.
+ * The pixel range is split into slabs of slab_rows consecutive image rows (of the N * Hin rows; the last slab may
+ * be partial, a slab may cross from one image into the next; slab_rows 0 = chosen by the library).  Within a slab the pixels are
+ * reduced in ascending order, 16 per step of v_mfma_f32_32x32x16_bf16, into one fp32 accumulator per element; the slabs' partial
+ * sums go to the workspace and a second kernel adds them in ascending slab order, reads only the entries whose input and output
+ * channel share a group (the off-group products of a 32-wide bundle never reach dw) and rounds once.  No floating-point atomics:
+ * the result is bit-identical from run to run.  Chain of a dw element: MFMA steps per slab (= ceil(slab_rows * Win / 16)) + 2 for
+ * the MFMA-internal sum + one add per slab.  The bias gradient is that of the "Trainable convolution" section on dy, partitioned
+ * by the same slab_rows over its N * Hout rows: ceil(slab_rows * Wout / 8) + 8 + slabs.
+ * cpn_grouped_conv_wgrad_info answers without touching the device, and rejects what the launch rejects:
+ *   info = {slabs, slab_rows, MFMA steps per slab, reduce chain (adds of the second kernel), chain of a bias element}.
+ * cpn_grouped_conv_wgrad: dz is the gradient at the input's size (dy itself at stride 1, the dilated one at stride 2), read for
+ * dw together with x; dy is read for db only.  dw or db may be NULL: that gradient is not computed and its operands may be NULL.
+ * x and dz start at 16-byte aligned addresses (CPN_E_INVALID otherwise).  workspace: cpn_grouped_conv_wgrad_workspace_bytes(...)
+ * bytes on the device for the same arguments (0 for arguments the call rejects); a smaller one is CPN_E_WORKSPACE.
+ * N * Hin * Win <= 2^31 - 1 and N * Hin * Win * C < 2^30 (CPN_E_UNSUPPORTED above: the limit of cpn_conv2d's sources).  Every
+ * launch validates before it touches a pointer.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_grouped_conv_pack(const void *w, int32_t w_dtype, int32_t C, int32_t cig, int32_t mode /* CPN_CONV_PACK_* */, void *packed,
+                          void *stream);
+int cpn_grouped_conv_dilate(const void *dy, int32_t N, int32_t Hin, int32_t Win, int32_t C, void *dz, void *stream);
+int64_t cpn_grouped_conv_wgrad_workspace_bytes(int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t cig, int32_t stride,
+                                               int32_t slab_rows);
+int cpn_grouped_conv_wgrad_info(int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t cig, int32_t stride, int32_t slab_rows,
+                                int32_t info[5]);
+int cpn_grouped_conv_wgrad(const void *x, const void *dz, const void *dy, int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t cig,
+                           int32_t stride, int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db, int32_t db_dtype,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
