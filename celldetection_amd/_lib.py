@@ -267,6 +267,12 @@ _SIGNATURES = [
     ('cpn_grouped_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     ('cpn_grouped_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                               c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    ('cpn_residual_bn_apply', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                             c_int32, c_void_p]),
+    ('cpn_residual_bn_backward_reduce', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64,
+                                                       c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                                       c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    ('cpn_subsample2d', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -16,6 +16,9 @@
 //   bn_apply_kernel<T, RELU>: y = fmaf(x, scale, shift), or its positive part.
 //   bn_grad_finalise_kernel:  adds the slabs; dbeta, dgamma and the input kernel's per-channel a, b, c.
 //   bn_input_kernel<T, RELU>: dx = fmaf(a, g, fmaf(b, x, c)) (training) or fmaf(a, g, 0) (eval).
+// The tail of a residual block ("Trainable bottleneck block" of include/cpn_hip.h), kernels of their own beside the ones above:
+//   bn_apply_residual_kernel<T, RELU>: y = fmaf(x, scale, shift) + r (an fp32 add), or its positive part.
+//   bn_sum_residual_kernel<T>:         g = dy [y > 0] written once (the residual's gradient) and the sums of modes 1 / 2 on it.
 // No floating-point atomics: results are bit-identical from run to run.
 #include <hip/hip_runtime.h>
 
@@ -332,6 +335,88 @@ __global__ __launch_bounds__(256) void bn_input_kernel(const T *__restrict__ x, 
     }
 }
 
+// The tail of a residual block ("Trainable bottleneck block" of include/cpn_hip.h): y = t + r or its positive part,
+// t = fmaf(x, scale, shift); the fp32 add is a rounding of its own, the store the only other one.
+template <typename T, bool RELU>
+__global__ __launch_bounds__(256) void bn_apply_residual_kernel(const T *__restrict__ x, const T *__restrict__ r, T *__restrict__ y,
+                                                                 const float *__restrict__ scale, const float *__restrict__ shift,
+                                                                 BnSlabs part, int C) {
+    const int block = blockIdx.y;
+    const int vb = bns_block_vectors(part, block), R = bns_rows(vb);
+    int row, vec;
+    if (!bns_lane(vb, threadIdx.x, &row, &vec)) return;
+    const int c0 = (block * BNS_LANES + vec) * BNS_VEC;
+    int64_t p0, p1;
+    bns_range(part, (int32_t) blockIdx.x, &p0, &p1);
+    float sc[8], sh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        sc[i] = scale[c0 + i];
+        sh[i] = shift[c0 + i];
+    }
+    for (int64_t p = p0 + row; p < p1; p += R) {
+        float v[8], rv[8];
+        bn_load8<T>(x, p, C, c0, v);
+        bn_load8<T>(r, p, C, c0, rv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float s = __builtin_fmaf(v[i], sc[i], sh[i]) + rv[i];
+            v[i] = RELU ? (s > 0.f ? s : 0.f) : s;
+        }
+        bn_store8<T>(y, p, C, c0, v);
+    }
+}
+
+// bn_sum_kernel's modes 1 / 2 with the mask of the stored output: g = dy [y > 0], written once to `g` (the residual's gradient),
+// and the same two fp64 sums (g, g x) in the same order into the same workspace layout.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_sum_residual_kernel(const T *__restrict__ x, const T *__restrict__ dy,
+                                                               const T *__restrict__ y, T *__restrict__ g,
+                                                               double *__restrict__ ws, BnSlabs part, int C) {
+    __shared__ double lds[BNS_LANES * 16];  // [lane][channel of the lane][2]
+    const int tid = threadIdx.x, block = blockIdx.y;
+    const int vb = bns_block_vectors(part, block), R = bns_rows(vb);
+    int row, vec;
+    const bool active = bns_lane(vb, tid, &row, &vec);
+    const int c0 = (block * BNS_LANES + vec) * BNS_VEC;
+    int64_t p0, p1;
+    bns_range(part, (int32_t) blockIdx.x, &p0, &p1);
+
+    double s0[8], s1[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s0[i] = s1[i] = 0.;
+    if (active) {
+        for (int64_t p = p0 + row; p < p1; p += R) {
+            float xv[8], gv[8], yv[8];
+            bn_load8<T>(x, p, C, c0, xv);
+            bn_load8<T>(dy, p, C, c0, gv);
+            bn_load8<T>(y, p, C, c0, yv);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
+                const double xd = (double) xv[i], gd = (double) gv[i];
+                s0[i] = s0[i] + gd;
+                s1[i] = s1[i] + gd * xd;
+            }
+            bn_store8<T>(g, p, C, c0, gv);  // (values of the dtype already: the rounding is the identity)
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        lds[tid * 16 + 2 * i] = s0[i];
+        lds[tid * 16 + 2 * i + 1] = s1[i];
+    }
+    __syncthreads();
+    const int rows = bns_partials(p1 - p0, vb);
+    double *out = ws + ((int64_t) blockIdx.x * C + (int64_t) block * BNS_LANES * BNS_VEC) * 2;
+    for (int item = tid; item < vb * 16; item += BNS_LANES) {  // as in bn_sum_kernel
+        const int v = item >> 4, j = item & 15;
+        double sum = lds[v * 16 + j];
+        for (int r = 1; r < rows; ++r) sum = sum + lds[(r * vb + v) * 16 + j];
+        out[item] = sum;
+    }
+}
+
 // 0, or the error code with its message recorded; the partition of an accepted call
 int bn_check(const char *who, int64_t M, int64_t C, int64_t slab_pixels, BnSlabs *part) {
     static thread_local char msg[200];
@@ -481,6 +566,63 @@ int cpn_bn_backward_reduce(const void *x, const void *dy, int32_t dtype, int64_t
     hipLaunchKernelGGL(bn_grad_finalise_kernel, dim3((unsigned) (C / 8)), dim3(256), 0, st, ws, part.slabs, (int) C, M, save_mean,
                        save_invstd, weight, weight_dtype, dgamma, dgamma_dtype, dbeta, dbeta_dtype, coeffs);
     return cpn::check_hip(hipGetLastError(), "cpn_bn_backward_reduce");
+}
+
+int cpn_residual_bn_apply(const void *x, const void *r, void *y, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels,
+                          const float *scale, const float *shift, int32_t relu, void *stream) {
+    BnSlabs part;
+    if (const int rc = bn_check("cpn_residual_bn_apply", M, C, slab_pixels, &part)) return rc;
+    if (!x || !r || !y || !scale || !shift) return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_apply: null pointer");
+    if (!bn_dtype_ok(dtype)) return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_apply: dtype must be 0 (fp32) or 1 (bf16)");
+    if (!bn_aligned(x, r, y)) return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_apply: x, r and y must be 16-byte aligned");
+    hipStream_t st = (hipStream_t) stream;
+#define BN_APPLY_RES(T, RELU)                                                                                                      \
+    hipLaunchKernelGGL((bn_apply_residual_kernel<T, RELU>), bn_grid(part), dim3(256), 0, st, (const T *) x, (const T *) r, (T *) y, \
+                       scale, shift, part, (int) C)
+    if (dtype == BN_BF16) {
+        if (relu) BN_APPLY_RES(uint16_t, true);
+        else BN_APPLY_RES(uint16_t, false);
+    } else {
+        if (relu) BN_APPLY_RES(float, true);
+        else BN_APPLY_RES(float, false);
+    }
+#undef BN_APPLY_RES
+    return cpn::check_hip(hipGetLastError(), "cpn_residual_bn_apply");
+}
+
+int cpn_residual_bn_backward_reduce(const void *x, const void *dy, const void *y, void *g, int32_t dtype, int64_t M, int64_t C,
+                                    int64_t slab_pixels, const float *scale, const float *shift, int32_t relu,
+                                    const float *save_mean, const float *save_invstd, const void *weight, int32_t weight_dtype,
+                                    void *dgamma, int32_t dgamma_dtype, void *dbeta, int32_t dbeta_dtype, float *coeffs,
+                                    void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!relu)  // g = dy: nothing to mask and nothing to write; y and g are not looked at
+        return cpn_bn_backward_reduce(x, dy, dtype, M, C, slab_pixels, scale, shift, 0, save_mean, save_invstd, weight, weight_dtype,
+                                      dgamma, dgamma_dtype, dbeta, dbeta_dtype, coeffs, workspace, workspace_bytes, stream);
+    BnSlabs part;
+    if (const int rc = bn_check("cpn_residual_bn_backward_reduce", M, C, slab_pixels, &part)) return rc;
+    const bool sums = dgamma || dbeta || coeffs;  // without them g alone is written and the sums are dropped
+    if (!x || !dy || !y || !g || !workspace || (sums && (!save_mean || !save_invstd)))
+        return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_backward_reduce: null pointer");
+    if (!bn_dtype_ok(dtype) || (weight && !bn_dtype_ok(weight_dtype)) || (dgamma && !bn_dtype_ok(dgamma_dtype)) ||
+        (dbeta && !bn_dtype_ok(dbeta_dtype)))
+        return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_backward_reduce: a dtype must be 0 (fp32) or 1 (bf16)");
+    if (workspace_bytes < bn_ws_bytes(part, C))
+        return cpn::fail(CPN_E_WORKSPACE, "cpn_residual_bn_backward_reduce: workspace smaller than cpn_bn_workspace_bytes");
+    if (!bn_aligned(x, dy, y, g) || !bn_aligned(workspace))
+        return cpn::fail(CPN_E_INVALID, "cpn_residual_bn_backward_reduce: x, dy, y, g and workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t) stream;
+    double *ws = (double *) workspace;
+    if (dtype == BN_BF16)
+        hipLaunchKernelGGL((bn_sum_residual_kernel<uint16_t>), bn_grid(part), dim3(256), 0, st, (const uint16_t *) x, (const uint16_t *) dy,
+                           (const uint16_t *) y, (uint16_t *) g, ws, part, (int) C);
+    else
+        hipLaunchKernelGGL((bn_sum_residual_kernel<float>), bn_grid(part), dim3(256), 0, st, (const float *) x, (const float *) dy,
+                           (const float *) y, (float *) g, ws, part, (int) C);
+    if (const int rc = cpn::check_hip(hipGetLastError(), "cpn_residual_bn_backward_reduce")) return rc;  // (as in cpn_bn_train_stats)
+    if (!sums) return 0;
+    hipLaunchKernelGGL(bn_grad_finalise_kernel, dim3((unsigned) (C / 8)), dim3(256), 0, st, ws, part.slabs, (int) C, M, save_mean,
+                       save_invstd, weight, weight_dtype, dgamma, dgamma_dtype, dbeta, dbeta_dtype, coeffs);
+    return cpn::check_hip(hipGetLastError(), "cpn_residual_bn_backward_reduce");
 }
 
 int cpn_bn_backward_input(const void *x, const void *dy, void *dx, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels,

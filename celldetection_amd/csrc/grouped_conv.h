@@ -112,3 +112,11 @@ GCV_HD int64_t gc_dilate_source(uint32_t u, uint32_t Hin, uint32_t Win, uint32_t
     const uint32_t Hout = (Hin - 1) / 2 + 1, Wout = (Win - 1) / 2 + 1;
     return (((int64_t) n * Hout + (y >> 1)) * Wout + (x >> 1)) * C8 + c;
 }
+
+// The gather back: 16-byte unit u (8 channels) of xs [N][Hout][Wout][C] -> the unit of x [N][Hin][Win][C] it copies, the pixel
+// (stride i, stride j) of the same image (stride >= 1; stride (Hout - 1) <= Hin - 1 for even and odd Hin).  u < 2^32.
+GCV_HD int64_t gc_subsample_source(uint32_t u, uint32_t Hin, uint32_t Win, uint32_t C8, uint32_t stride) {
+    const uint32_t Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;
+    const uint32_t c = u % C8, p = u / C8, j = p % Wout, r = p / Wout, i = r % Hout, n = r / Hout;
+    return (((int64_t) n * Hin + (int64_t) i * stride) * Win + (int64_t) j * stride) * C8 + c;
+}

@@ -7,6 +7,8 @@
 //                          swapped inside the group); off-group entries and the padding item of every bundle are exact zeros.
 //   gc_dilate_kernel:      stride 2: dZ [N][Hin][Win][C], dZ[2 i][2 j] = dY[i][j] and zero elsewhere, 16 bytes per lane; every unit
 //                          of dZ is written exactly once (no separate clear).
+//   gc_subsample_kernel:   the gather back, xs[i][j] = x[2 i][2 j], 16 bytes per lane: the operand of the strided 1x1 shortcut's
+//                          weight gradient (cpn_subsample2d, "Trainable bottleneck block" of include/cpn_hip.h).
 // Weight gradient, dW[co][cl][ky][kx] = sum over pixels p of dZ[p][co] * X[p + (ky - 1) * W + (kx - 1)][g(co) * cig + cl]:
 //   gc_wgrad_slab_kernel:  the method of ct_wgrad_slab_kernel (csrc/conv_train.hip) on the diagonal fragments only.  One workgroup =
 //                          (slab of the pixel range, span of four fragments, filter row ky); a wave owns ONE diagonal 32 x 32
@@ -60,6 +62,14 @@ __global__ __launch_bounds__(256) void gc_dilate_kernel(const u32x4 *__restrict_
     u32x4 v = {0, 0, 0, 0};
     if (s >= 0) v = dy[s];
     dz[u] = v;
+}
+
+// xs [N][Hout][Wout][C], xs[i][j] = x[stride i][stride j]: every unit of xs written exactly once
+__global__ __launch_bounds__(256) void gc_subsample_kernel(const u32x4 *__restrict__ x, u32x4 *__restrict__ xs, unsigned Hin,
+                                                            unsigned Win, unsigned C8, unsigned stride, unsigned total) {
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= total) return;
+    xs[u] = x[gc_subsample_source(u, Hin, Win, C8, stride)];
 }
 
 // LDS image of the slab kernel: dZ [4 blocks][CH rows], X [4 blocks][CH + 2 rows], one row of zeros, the column of every chunk
@@ -259,6 +269,21 @@ int cpn_grouped_conv_dilate(const void *dy, int32_t N, int32_t Hin, int32_t Win,
     hipLaunchKernelGGL(gc_dilate_kernel, dim3((total + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const u32x4 *) dy,
                        (u32x4 *) dz, (unsigned) Hin, (unsigned) Win, (unsigned) (C / 8), total);
     return cpn::check_hip(hipGetLastError(), "cpn_grouped_conv_dilate");
+}
+
+int cpn_subsample2d(const void *x, int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t stride, void *xs, void *stream) {
+    if (N < 1 || Hin < 1 || Win < 1) return cpn::fail(CPN_E_INVALID, "cpn_subsample2d: N, H and W must be at least 1");
+    if (C < 8 || C % 8) return cpn::fail(CPN_E_INVALID, "cpn_subsample2d: C must be a positive multiple of 8");
+    if (stride != 2) return cpn::fail(CPN_E_INVALID, "cpn_subsample2d: stride must be 2");
+    // (the limits of the dilation: x is a source of cpn_conv2d, and the unit index stays in 32 bits)
+    if ((int64_t) N * Hin * Win > 0x7fffffffll || (int64_t) N * Hin * Win * C >= (1ll << 30))
+        return cpn::fail(CPN_E_UNSUPPORTED, "cpn_subsample2d: more than 2^31 - 1 pixels or 2^30 or more activation elements");
+    if (!x || !xs) return cpn::fail(CPN_E_INVALID, "cpn_subsample2d: null pointer");
+    if (((uintptr_t) x | (uintptr_t) xs) & 15) return cpn::fail(CPN_E_INVALID, "cpn_subsample2d: x and xs must be 16-byte aligned");
+    const unsigned total = (unsigned) ((int64_t) N * gc_out_size(Hin, stride) * gc_out_size(Win, stride) * (C / 8));
+    hipLaunchKernelGGL(gc_subsample_kernel, dim3((total + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const u32x4 *) x,
+                       (u32x4 *) xs, (unsigned) Hin, (unsigned) Win, (unsigned) (C / 8), (unsigned) stride, total);
+    return cpn::check_hip(hipGetLastError(), "cpn_subsample2d");
 }
 
 int64_t cpn_grouped_conv_wgrad_workspace_bytes(int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t cig, int32_t stride,

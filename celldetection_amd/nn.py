@@ -17,8 +17,7 @@ Supported: ``groups = 1``, ``stride = 1``, ``dilation = 1``, a square odd ``k`` 
 ``Cin`` and ``Cout`` multiples of 32, a 4-D input on the GPU.  Everything else raises ``NotImplementedError`` naming the argument;
 there is no CPU fallback.  ``convert_conv2d_`` leaves every other conv and says why: the grouped 3x3 convs of the encoder are the
 business of ``grouped_conv2d``, the final 1x1 convs of the heads (1 / 2 / 20 output channels) of ``dropout_conv1x1``, both below.
-Known limit: the stem, the max-pool, the strided 1x1 shortcuts and the residual add of the encoder, and the nearest resize with
-concat in the decoder, stay stock torch operations.
+Known limit: the stem, the max-pool and the nearest resize with concat in the decoder stay stock torch operations.
 
 Arithmetic: activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32, the forward output
 and the input gradient are stored as bf16, the weight and bias gradients are fp32 sums rounded once to the parameter's dtype.  ``x``
@@ -40,6 +39,13 @@ The grouped 3x3 ``conv2`` of the ResNeXt encoder's bottleneck blocks, at stride 
 ``torch.autograd.Function``), the ``nn.Conv2d`` drop-in ``GroupedConv2d`` and ``convert_grouped_conv2d_`` (fourth part of this
 module; the rule is the "Trainable grouped convolution" section of include/cpn_hip.h).  The 1x1 ``conv1`` / ``conv3`` around it are
 dense stride-1 convs that ``convert_conv2d_`` takes.
+
+The whole bottleneck block runs here: ``Bottleneck`` and ``convert_bottleneck_`` (last part of this module; the rule is the
+"Trainable bottleneck block" section of include/cpn_hip.h) put the convs and norms above together with the norm's residual tail
+(``batch_norm(..., residual=)``: ``relu(bn3(h) + identity)`` in one pass), the strided 1x1 shortcut of a stage entry
+(``strided_conv1x1``) and the block-input gradient in the epilogue of ``conv1``'s input-gradient conv (``conv2d_fork``).  Known limits:
+at a stage entry the shortcut's norm and the tail are two kernels (``relu(bn3(h) + bn_d(h_d))`` is not one pass); the stem, the
+max-pool, the decoder's resize + concat and the bilinear resize behind the heads stay stock; ``cda.models.*`` stay inference-only.
 """
 import ctypes
 
@@ -52,7 +58,8 @@ __all__ = ['conv2d', 'Conv2d', 'convert_conv2d_', 'is_supported', 'pack_weight',
            'batch_norm', 'batch_norm_forward', 'batch_norm_info', 'BatchNorm2d', 'convert_batchnorm2d_',
            'dropout_conv1x1', 'dropout_conv1x1_backward', 'readout_tail_info', 'DropoutConv1x1', 'convert_readout_tail_',
            'grouped_conv2d', 'GroupedConv2d', 'convert_grouped_conv2d_', 'grouped_weight_grad_info', 'grouped_conv2d_weight_grad',
-           'grouped_pack_weight', 'grouped_dilate']
+           'grouped_pack_weight', 'grouped_dilate',
+           'conv2d_fork', 'strided_conv1x1', 'StridedConv1x1', 'subsample2d', 'Bottleneck', 'convert_bottleneck_']
 
 KERNEL_SIZES = (1, 3, 5, 7)
 _DTYPES = {torch.float32: _lib.CONV_TRAIN_F32, torch.bfloat16: _lib.CONV_TRAIN_BF16}
@@ -113,15 +120,24 @@ def pack_weight(weight, mode='forward'):
     return packed
 
 
-def _run_conv(src, packed, bias, cin, cout, k):
-    """cpn_conv2d on a bf16 tensor whose memory is NHWC -> bf16 [N, cout, H, W] in channels_last."""
+def _run_conv(src, packed, bias, cin, cout, k, res=None, stride=1):
+    """cpn_conv2d on a bf16 tensor whose memory is NHWC -> bf16 [N, cout, Hout, Wout] in channels_last.  ``res``: a bf16 NHWC tensor
+    of the output's shape added to the fp32 sum before the one rounding; ``stride`` 2: the pointwise conv (k = 1) only."""
     n, _, h, w = src.shape
-    out = torch.empty((n, cout, h, w), dtype=torch.bfloat16, device=src.device, memory_format=torch.channels_last)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    out = torch.empty((n, cout, ho, wo), dtype=torch.bfloat16, device=src.device, memory_format=torch.channels_last)
     if out.numel() == 0:
         return out
     d = _conv_desc(cin, cout, k, bias is not None)
-    _lib.check(_lib.load().cpn_conv2d(ctypes.byref(d), _lib.ptr(src), cin, _lib.ptr(None), 0, _lib.ptr(None), 0, _lib.ptr(out), cout,
-                                      n, h, w, _lib.ptr(packed), _lib.ptr(bias), _lib.stream_ptr()), 'conv2d')
+    res_stride = 0
+    if stride != 1:
+        assert k == 1, (k, stride)
+        d.stride = stride
+    if res is not None:
+        assert tuple(res.shape) == tuple(out.shape) and res.dtype == torch.bfloat16, (tuple(res.shape), res.dtype)
+        d.res, res_stride = 2, cout
+    _lib.check(_lib.load().cpn_conv2d(ctypes.byref(d), _lib.ptr(src), cin, _lib.ptr(None), 0, _lib.ptr(res), res_stride, _lib.ptr(out),
+                                      cout, n, h, w, _lib.ptr(packed), _lib.ptr(bias), _lib.stream_ptr()), 'conv2d')
     return out
 
 
@@ -189,9 +205,7 @@ class _Conv2dFunction(torch.autograd.Function):
         return dx, dw, db
 
 
-def conv2d(x, weight, bias=None, padding=None):
-    """``torch.nn.functional.conv2d(x, weight, bias, stride=1, padding=k // 2)`` for the supported family (module docstring), with
-    gradients for ``x``, ``weight`` and ``bias`` as autograd asks for them -> bf16 [N, Cout, H, W] in ``torch.channels_last``."""
+def _check_conv2d(x, weight, bias, padding=None):
     if x.dim() != 4:
         raise NotImplementedError(f'input of {x.dim()} dimensions: the trainable conv takes a 4-D [N, C, H, W] input')
     _check_weight(weight)
@@ -207,7 +221,51 @@ def conv2d(x, weight, bias=None, padding=None):
     if bias is not None and (bias.dim() != 1 or bias.shape[0] != weight.shape[0] or bias.dtype not in _DTYPES):
         raise NotImplementedError(f'bias {tuple(bias.shape)} {bias.dtype}: the trainable conv takes a float32 or bfloat16 [Cout] bias')
     _need_cuda(x, weight, bias)
+
+
+def conv2d(x, weight, bias=None, padding=None):
+    """``torch.nn.functional.conv2d(x, weight, bias, stride=1, padding=k // 2)`` for the supported family (module docstring), with
+    gradients for ``x``, ``weight`` and ``bias`` as autograd asks for them -> bf16 [N, Cout, H, W] in ``torch.channels_last``."""
+    _check_conv2d(x, weight, bias, padding)
     return _Conv2dFunction.apply(x, weight, bias)
+
+
+class _Conv2dForkFunction(torch.autograd.Function):
+    """``conv2d`` whose second output is its input: the gradient that arrives there is added in the dgrad conv's epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.set_materialize_grads(False)  # an absent skip gradient arrives as None, not as a tensor of zeros
+        return _Conv2dFunction.forward(ctx, x, weight, bias), x  # (an input returned as it is becomes an alias of it)
+
+    @staticmethod
+    def backward(ctx, grad_output, grad_skip):
+        if grad_skip is None:
+            return (None, None, None) if grad_output is None else _Conv2dFunction.backward(ctx, grad_output)
+        if grad_output is None:
+            return (grad_skip.to(ctx.x_dtype) if ctx.needs_input_grad[0] else None), None, None
+        xs, weight = ctx.saved_tensors
+        cout, cin, k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+        need_x, need_w, need_b = ctx.needs_input_grad
+        need_b = need_b and ctx.bias_dtype is not None
+        gs = _nhwc_bf16(grad_output.detach())
+        dx = dw = db = None
+        if need_x:  # the dgrad conv with the skip's gradient as its residual operand: the sum in fp32, one rounding
+            dx = _run_conv(gs, pack_weight(weight, 'dgrad'), None, cout, cin, k, res=_nhwc(grad_skip, torch.bfloat16)).to(ctx.x_dtype)
+        if need_w or need_b:
+            dw, db = conv2d_weight_grad(xs, gs, k, weight=need_w, bias=need_b, dtype=weight.dtype,
+                                        bias_dtype=ctx.bias_dtype or weight.dtype)
+        return dx, dw, db
+
+
+def conv2d_fork(x, weight, bias=None):
+    """``conv2d(x, weight, bias)`` at the head of a residual block -> ``(y, skip)``: ``y`` is ``conv2d``'s output bit for bit,
+    ``skip`` is ``x`` (same storage, no copy) with this function as its ``grad_fn``, so autograd sees ONE consumer of ``x`` and the
+    two gradients of the block's input are never added by a stock op: when a gradient arrives at ``skip`` it is rounded to bf16
+    channels-last as ``grad_output`` is and becomes the residual operand of the dgrad conv, ``dx = round(dgrad(dy) + dskip)`` with
+    the sum in fp32; when none arrives the backward is ``conv2d``'s."""
+    _check_conv2d(x, weight, bias)
+    return _Conv2dForkFunction.apply(x, weight, bias)
 
 
 def _pair(v):
@@ -271,8 +329,8 @@ class Conv2d(torch.nn.Conv2d):
             raise NotImplementedError(why)
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device, dtype)
 
-    def forward(self, x):
-        return conv2d(x, self.weight, self.bias)
+    def forward(self, x, fork=False):
+        return conv2d_fork(x, self.weight, self.bias) if fork else conv2d(x, self.weight, self.bias)
 
 
 def _from_torch(conv):
@@ -287,12 +345,13 @@ def convert_conv2d_(module):
     (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).  ``module`` itself is not replaced
     when it is a conv: it is reported as left."""
     replaced, left = [], {}
-    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, Conv2d):
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, StridedConv1x1)):
         left[''] = _why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     for name, parent in list(module.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f'{name}.{child_name}' if name else child_name
-            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d)) or not isinstance(child, torch.nn.modules.conv._ConvNd):
+            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1)) or \
+                    not isinstance(child, torch.nn.modules.conv._ConvNd):
                 continue
             why = _why_not(child) if isinstance(child, torch.nn.Conv2d) else f'{type(child).__name__}: 2-D convs only'
             if why is None:
@@ -309,8 +368,9 @@ def convert_conv2d_(module):
 # function on the channels-last tensor the conv hands over: statistics (1 read), apply (1 read, 1 write), backward reduce (2 reads),
 # backward input (2 reads, 1 write).  It saves ``x`` and per-channel fp32 vectors only: the ReLU mask is recomputed bit for bit from
 # ``x`` by the forward's own fma.  Sums over pixels are fp64 in a fixed order (no floating-point atomics); supported: a 4-D input
-# on the GPU, float32 or bfloat16, ``C`` a positive multiple of 8.  Known limits: no residual add before the ReLU, statistics not
-# folded into the conv epilogue.
+# on the GPU, float32 or bfloat16, ``C`` a positive multiple of 8.  With ``residual`` the apply adds it before the ReLU (3 passes) and
+# the backward masks by the stored output (4 + 3 passes; ``x`` and ``y`` saved).  Known limit: statistics not folded into the conv
+# epilogue.
 
 ACTIVATIONS = (None, 'relu')
 _INFO_KEYS = ('slabs', 'slab_pixels', 'rows', 'channel_blocks', 'chain')
@@ -365,8 +425,9 @@ def _workspace(lib, m, c, slab_pixels, device):
     return torch.empty((nbytes,), dtype=torch.uint8, device=device), nbytes
 
 
-def _bn_forward(xs, running_mean, running_var, weight, bias, use_batch, momentum, eps, relu, slab_pixels):
-    """xs: channels-last, on the GPU -> (y, save_mean, save_invstd, scale, shift); updates the running buffers when use_batch."""
+def _bn_forward(xs, running_mean, running_var, weight, bias, use_batch, momentum, eps, relu, slab_pixels, residual=None):
+    """xs (and residual, if any, of its dtype and shape): channels-last, on the GPU -> (y, save_mean, save_invstd, scale, shift);
+    updates the running buffers when use_batch."""
     n, c, h, w = (int(v) for v in xs.shape)
     m = n * h * w
     lib = _lib.load()
@@ -383,13 +444,24 @@ def _bn_forward(xs, running_mean, running_var, weight, bias, use_batch, momentum
         _lib.check(lib.cpn_bn_eval_coeffs(c, _lib.ptr(weight), _dt(weight), _lib.ptr(bias), _dt(bias), _lib.ptr(running_mean),
                                           _lib.ptr(running_var), _dt(running_mean), float(eps), _lib.ptr(mean), _lib.ptr(invstd),
                                           _lib.ptr(scale), _lib.ptr(shift), _lib.stream_ptr()), 'bn_eval_coeffs')
+    if residual is not None:
+        _lib.check(lib.cpn_residual_bn_apply(_lib.ptr(xs), _lib.ptr(residual), _lib.ptr(y), _dt(xs), m, c, slab_pixels, _lib.ptr(scale),
+                                             _lib.ptr(shift), int(relu), _lib.stream_ptr()), 'bn_apply_residual')
+        return y, mean, invstd, scale, shift
     _lib.check(lib.cpn_bn_apply(_lib.ptr(xs), _lib.ptr(y), _dt(xs), m, c, slab_pixels, _lib.ptr(scale), _lib.ptr(shift), int(relu),
                                 _lib.stream_ptr()), 'bn_apply')
     return y, mean, invstd, scale, shift
 
 
-def _prepare(x, running_mean, running_var, weight, bias, training, activation):
+def _prepare(x, running_mean, running_var, weight, bias, training, activation, residual=None):
     _check_bn(x, running_mean, running_var, weight, bias, activation)
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or tuple(residual.shape) != tuple(x.shape):
+            raise NotImplementedError(f'residual of shape {tuple(getattr(residual, "shape", ()))}: the batch norm adds a tensor of the '
+                                      f"input's shape {tuple(x.shape)}")
+        if residual.dtype not in _DTYPES:
+            raise NotImplementedError(f'residual dtype {residual.dtype}: the batch norm adds a float32 or bfloat16 tensor')
+        _need_cuda(residual)
     use_batch = bool(training) or running_mean is None
     n, c, h, w = (int(v) for v in x.shape)
     if use_batch and n * h * w == 1:
@@ -401,14 +473,16 @@ def _prepare(x, running_mean, running_var, weight, bias, training, activation):
 
 
 def batch_norm_forward(x, running_mean, running_var, weight=None, bias=None, training=False, momentum=0.1, eps=1e-5,
-                       activation=None, slab_pixels=0):
+                       activation=None, slab_pixels=0, residual=None):
     """The forward of ``batch_norm`` without autograd -> (y, save_mean, save_invstd, scale, shift): ``y`` in ``x``'s dtype and
     ``torch.channels_last``, four fp32 ``[C]`` vectors (eval: the running mean, its invstd and the coefficients from them).  In
-    training the running buffers are updated in place.  ``slab_pixels``: pixels per slab of the sums (0: chosen by the library)."""
-    use_batch = _prepare(x, running_mean, running_var, weight, bias, training, activation)
+    training the running buffers are updated in place.  ``slab_pixels``: pixels per slab of the sums (0: chosen by the library).
+    ``residual``: as in ``batch_norm``."""
+    use_batch = _prepare(x, running_mean, running_var, weight, bias, training, activation, residual)
     det = [None if t is None else t.detach().contiguous() for t in (weight, bias)]
     xs = _nhwc(x)
-    return _bn_forward(xs, running_mean, running_var, det[0], det[1], use_batch, momentum, eps, activation == 'relu', slab_pixels)
+    rs = None if residual is None else _nhwc(residual, xs.dtype)
+    return _bn_forward(xs, running_mean, running_var, det[0], det[1], use_batch, momentum, eps, activation == 'relu', slab_pixels, rs)
 
 
 class _BatchNormFunction(torch.autograd.Function):
@@ -453,16 +527,83 @@ class _BatchNormFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None, None
 
 
+class _BatchNormResidualFunction(torch.autograd.Function):
+    """activation(bn(x) + residual).  Saves x, its own output y and the per-channel vectors -- not the residual: the ReLU mask is
+    ``y > 0`` on the stored output, as in torch's own ReLU backward."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, use_batch, momentum, eps, relu, slab_pixels):
+        xs = _nhwc(x)
+        rs = _nhwc(residual, xs.dtype)
+        wd = None if weight is None else weight.detach().contiguous()
+        bd = None if bias is None else bias.detach().contiguous()
+        y, mean, invstd, scale, shift = _bn_forward(xs, running_mean, running_var, wd, bd, use_batch, momentum, eps, relu, slab_pixels,
+                                                    rs)
+        ctx.save_for_backward(xs, y, weight, mean, invstd, scale, shift)
+        ctx.use_batch, ctx.relu, ctx.slab_pixels = use_batch, relu, slab_pixels
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.residual_dtype = residual.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        xs, y, weight, mean, invstd, scale, shift = ctx.saved_tensors
+        need_x, need_r, need_w, need_b = ctx.needs_input_grad[:4]
+        need_w = need_w and weight is not None
+        need_b = need_b and ctx.bias_dtype is not None
+        n, c, h, w = (int(v) for v in xs.shape)
+        m, sp = n * h * w, ctx.slab_pixels
+        lib = _lib.load()
+        gs = _nhwc(grad_output, xs.dtype)
+        wd = None if weight is None else weight.detach().contiguous()
+        dx = dw = db = abc = None
+        sums = need_w or need_b or (need_x and ctx.use_batch)
+        g = gs  # without ReLU g = dy: nothing is masked and nothing is written
+        if sums or (ctx.relu and (need_x or need_r)):
+            dw = torch.empty((c,), dtype=weight.dtype, device=xs.device) if need_w else None
+            db = torch.empty((c,), dtype=ctx.bias_dtype, device=xs.device) if need_b else None
+            abc = torch.empty((3, c), dtype=torch.float32, device=xs.device) if need_x and ctx.use_batch else None
+            if ctx.relu:
+                g = torch.empty_like(xs, memory_format=torch.channels_last)
+            ws, nbytes = _workspace(lib, m, c, sp, xs.device)
+            _lib.check(lib.cpn_residual_bn_backward_reduce(_lib.ptr(xs), _lib.ptr(gs), _lib.ptr(y), _lib.ptr(g), _dt(xs), m, c, sp,
+                                                           _lib.ptr(scale), _lib.ptr(shift), int(ctx.relu), _lib.ptr(mean),
+                                                           _lib.ptr(invstd), _lib.ptr(wd), _dt(wd), _lib.ptr(dw), _dt(dw), _lib.ptr(db),
+                                                           _dt(db), _lib.ptr(abc), _lib.ptr(ws), nbytes, _lib.stream_ptr()),
+                       'bn_backward_reduce_residual')
+        if need_x:
+            dx = torch.empty_like(xs, memory_format=torch.channels_last)
+            a, b, cc = (abc[0], abc[1], abc[2]) if ctx.use_batch else (scale, None, None)
+            _lib.check(lib.cpn_bn_backward_input(_lib.ptr(xs), _lib.ptr(g), _lib.ptr(dx), _dt(xs), m, c, sp, _lib.ptr(None),
+                                                 _lib.ptr(None), 0, _lib.ptr(a), _lib.ptr(b), _lib.ptr(cc), _lib.stream_ptr()),
+                       'bn_backward_input')
+        dr = g.to(ctx.residual_dtype) if need_r else None
+        return dx, dr, dw, db, None, None, None, None, None, None, None
+
+
 def batch_norm(x, running_mean, running_var, weight=None, bias=None, training=False, momentum=0.1, eps=1e-5, activation=None,
-               slab_pixels=0):
+               slab_pixels=0, residual=None):
     """``torch.nn.functional.batch_norm`` (its argument order) for a 4-D input on the GPU, followed by ``activation`` (None |
     'relu') in the same kernels, with gradients for ``x``, ``weight`` and ``bias`` as autograd asks for them -> ``x``'s dtype in
     ``torch.channels_last``.  Batch statistics are used when ``training`` or when the running buffers are absent; in training the
     running buffers are updated in place with ``momentum``.  Anything unsupported raises ``NotImplementedError`` naming the
-    argument; training on a single value per channel raises ``ValueError`` like torch."""
-    use_batch = _prepare(x, running_mean, running_var, weight, bias, training, activation)
+    argument; training on a single value per channel raises ``ValueError`` like torch.
+
+    ``residual`` (``[N, C, H, W]``, float32 | bfloat16, brought to ``x``'s dtype and channels-last as ``grad_output`` is): the tail
+    of a residual block, ``activation(bn(x) + residual)`` in one pass behind the unchanged statistics: ``t = fmaf(x, scale, shift)``
+    and ``t + residual`` are fp32 operations, the result is rounded once to the dtype.  Its backward takes the ReLU mask from the
+    stored output (``y > 0``), so it saves ``x`` and its own output ``y``, which the next conv saves anyway, and not ``residual``; an
+    in-place operation on ``y`` downstream therefore makes autograd raise.  The masked gradient is the residual's gradient bit for
+    bit (returned in ``residual``'s dtype).  ``residual=None``: the same launches and bits as without the argument."""
+    use_batch = _prepare(x, running_mean, running_var, weight, bias, training, activation, residual)
+    if residual is not None:
+        return _BatchNormResidualFunction.apply(x, residual, weight, bias, running_mean, running_var, use_batch, float(momentum),
+                                                float(eps), activation == 'relu', int(slab_pixels))
     return _BatchNormFunction.apply(x, weight, bias, running_mean, running_var, use_batch, float(momentum), float(eps),
                                     activation == 'relu', int(slab_pixels))
+
+
+_MODULE_S = object()  # BatchNorm2d.forward(activation=...): "the module's own"
 
 
 class BatchNorm2d(torch.nn.BatchNorm2d):
@@ -479,7 +620,9 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
         super().__init__(num_features, eps, momentum, affine, track_running_stats, device, dtype)
         self.activation = activation
 
-    def forward(self, x):
+    def forward(self, x, residual=None, activation=_MODULE_S):
+        """``residual``, ``activation`` (default: the module's): as in ``batch_norm``, for this call."""
+        activation = self.activation if activation is _MODULE_S else activation
         factor = 0. if self.momentum is None else self.momentum
         if self.training and self.track_running_stats and self.num_batches_tracked is not None:
             self.num_batches_tracked.add_(1)
@@ -487,7 +630,7 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
                 factor = 1. / float(self.num_batches_tracked)
         use_buffers = not self.training or self.track_running_stats
         return batch_norm(x, self.running_mean if use_buffers else None, self.running_var if use_buffers else None, self.weight,
-                          self.bias, self.training or self.running_mean is None, factor, self.eps, self.activation)
+                          self.bias, self.training or self.running_mean is None, factor, self.eps, activation, residual=residual)
 
     def extra_repr(self):
         return super().extra_repr() + f', activation={self.activation!r}'
@@ -783,7 +926,7 @@ def convert_readout_tail_(module):
         for child in parent._modules.values():
             if type(child) in (torch.nn.Dropout2d, torch.nn.Conv2d):
                 uses[id(child)] = uses.get(id(child), 0) + 1
-    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, DropoutConv1x1)) and \
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, DropoutConv1x1, StridedConv1x1)) and \
             _pair(module.kernel_size) == (1, 1):
         left[''] = _tail_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
@@ -791,7 +934,7 @@ def convert_readout_tail_(module):
         slots = [(n, c) for n, c in parent._modules.items() if c is not None]  # (named_children() drops repeated objects)
         for i, (child_name, child) in enumerate(slots):
             full = f'{name}.{child_name}' if name else child_name
-            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, (Conv2d, DropoutConv1x1)) or \
+            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, (Conv2d, DropoutConv1x1, StridedConv1x1)) or \
                     _pair(child.kernel_size) != (1, 1):
                 continue
             why = _tail_why_not(child)
@@ -1069,7 +1212,7 @@ def convert_grouped_conv2d_(module):
     when it is such a conv: it is reported as left.  A conv object that sits in several slots is replaced by one object in all of
     them.  Works before or after the other converts."""
     replaced, left = [], {}
-    ours = (Conv2d, DropoutConv1x1, GroupedConv2d)
+    ours = (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1)
     if isinstance(module, torch.nn.Conv2d) and not isinstance(module, ours) and module.groups > 1:
         left[''] = _grouped_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
@@ -1086,5 +1229,336 @@ def convert_grouped_conv2d_(module):
             if id(child) not in swapped:
                 swapped[id(child)] = _grouped_from_torch(child)
             setattr(parent, child_name, swapped[id(child)])
+            replaced.append(full)
+    return replaced, left
+
+
+# ---- the bottleneck block of a ResNeXt encoder ("Trainable bottleneck block" of include/cpn_hip.h)
+#
+# Three pieces beside the convs and norms above make a whole block run here: the norm's residual tail (``batch_norm(...,
+# residual=)``), the strided 1x1 shortcut conv of a stage entry (``strided_conv1x1``) and the block-input gradient in the epilogue of
+# conv1's dgrad conv (``conv2d_fork``).  ``Bottleneck`` puts them together, ``convert_bottleneck_`` swaps eligible blocks in place.
+
+def subsample2d(x, stride=2):
+    """x [N, C, H, W] -> bf16 ``x[..., ::2, ::2]`` in ``torch.channels_last`` by one 16-byte-per-lane gather (``C`` a positive
+    multiple of 8): the operand of the strided shortcut's weight gradient."""
+    if x.dim() != 4:
+        raise NotImplementedError(f'input of {x.dim()} dimensions: the subsample takes a 4-D [N, C, H, W] input')
+    n, c, h, w = (int(v) for v in x.shape)
+    if c < 8 or c % 8:
+        raise NotImplementedError(f'input of {c} channels: the subsample needs a positive multiple of 8')
+    if stride != 2:
+        raise NotImplementedError(f'stride {stride}: the subsample runs stride 2 only')
+    _need_cuda(x)
+    xs = _nhwc(x, torch.bfloat16)
+    out = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.bfloat16, device=xs.device, memory_format=torch.channels_last)
+    if out.numel():
+        _lib.check(_lib.load().cpn_subsample2d(_lib.ptr(xs), n, h, w, c, 2, _lib.ptr(out), _lib.stream_ptr()), 'subsample2d')
+    return out
+
+
+def _check_strided(weight, stride):
+    """Raises NotImplementedError naming the argument the strided shortcut does not run."""
+    _check_weight(weight)
+    if int(weight.shape[2]) != 1:
+        raise NotImplementedError(f'kernel_size {int(weight.shape[2])}: the strided shortcut conv is 1x1')
+    if _pair(stride) != (2, 2):
+        raise NotImplementedError(f'stride {stride}: the strided shortcut conv runs stride 2 only')
+
+
+class _StridedConv1x1Function(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        xs = _nhwc(x, torch.bfloat16)
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        out = _run_conv(xs, pack_weight(weight, 'forward'), b32, cin, cout, 1, stride=2)  # the pointwise tile gathers its outputs
+        ctx.save_for_backward(xs, weight)
+        ctx.x_dtype = x.dtype
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        xs, weight = ctx.saved_tensors
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        need_x, need_w, need_b = ctx.needs_input_grad
+        need_b = need_b and ctx.bias_dtype is not None
+        gs = _nhwc(grad_output, torch.bfloat16)
+        dx = dw = db = None
+        if need_x:  # the stride-1 dgrad conv at the small size, then the scatter onto the even grid of the input's size
+            small = _run_conv(gs, pack_weight(weight, 'dgrad'), None, cout, cin, 1)
+            dx = grouped_dilate(small, xs.shape[2:]).to(ctx.x_dtype)
+        if need_w or need_b:  # dW(x, dy) = dW_dense(x[::2, ::2], dy); the gather runs only when dW is asked for
+            sub = subsample2d(xs) if need_w else torch.empty((xs.shape[0], cin) + tuple(gs.shape[2:]), dtype=torch.bfloat16,
+                                                             device=xs.device, memory_format=torch.channels_last)
+            dw, db = conv2d_weight_grad(sub, gs, 1, weight=need_w, bias=need_b, dtype=weight.dtype,
+                                        bias_dtype=ctx.bias_dtype or weight.dtype)
+        return dx, dw, db
+
+
+def strided_conv1x1(x, weight, bias=None, stride=2):
+    """``torch.nn.functional.conv2d(x, weight, bias, stride=2)`` for a 1x1 ``weight`` ``[Cout, Cin, 1, 1]``, ``Cin`` and ``Cout``
+    multiples of 32: the shortcut conv at a stage entry of the encoder, with gradients for ``x``, ``weight`` and ``bias`` as autograd
+    asks for them -> bf16 ``[N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1]`` in ``torch.channels_last``.  Arithmetic and layout are
+    ``conv2d``'s.  The forward reads ``x`` itself (no gathered copy); the input gradient is the 1x1 dgrad conv of ``grad_output`` at
+    the small size scattered onto the even grid (exact zeros elsewhere); the weight gradient is ``conv2d_weight_grad`` on
+    ``subsample2d(x)``.  Anything else raises ``NotImplementedError`` naming the argument; there is no fallback."""
+    if x.dim() != 4:
+        raise NotImplementedError(f'input of {x.dim()} dimensions: the strided shortcut conv takes a 4-D [N, C, H, W] input')
+    _check_strided(weight, stride)
+    if x.dtype not in _DTYPES:
+        raise NotImplementedError(f'input dtype {x.dtype}: the strided shortcut conv takes float32 or bfloat16 activations')
+    if int(x.shape[1]) != int(weight.shape[1]):
+        raise ValueError(f'input has {int(x.shape[1])} channels, weight expects {int(weight.shape[1])}')
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != weight.shape[0] or bias.dtype not in _DTYPES):
+        raise NotImplementedError(f'bias {tuple(bias.shape)} {bias.dtype}: the strided shortcut conv takes a float32 or bfloat16 '
+                                  f'[Cout] bias')
+    _need_cuda(x, weight, bias)
+    if x.shape[0] * x.shape[2] * x.shape[3] == 0:
+        raise NotImplementedError(f'input of shape {tuple(x.shape)}: the strided shortcut conv needs at least one pixel')
+    return _StridedConv1x1Function.apply(x, weight, bias)
+
+
+def _strided_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels, transposed=False):
+    """The first argument ``StridedConv1x1`` does not run, as a sentence, or None."""
+    if transposed:
+        return 'transposed convs are not run'
+    if _pair(kernel_size) != (1, 1):
+        return f'kernel_size {kernel_size}: 1x1 only'
+    if _pair(stride) != (2, 2):
+        return f'stride {stride}: stride 2 only'
+    if groups != 1:
+        return f'groups {groups}: dense convs only'
+    if _pair(dilation) != (1, 1):
+        return f'dilation {dilation}: dilation 1 only'
+    if padding != 'valid' and (isinstance(padding, str) or _pair(padding) != (0, 0)):
+        return f'padding {padding!r}: no padding only'
+    if padding_mode != 'zeros':
+        return f"padding_mode '{padding_mode}': zeros only"
+    if in_channels < 32 or in_channels % 32:
+        return f'in_channels {in_channels}: multiples of 32 only'
+    if out_channels < 32 or out_channels % 32:
+        return f'out_channels {out_channels}: multiples of 32 only'
+    return None
+
+
+class StridedConv1x1(torch.nn.Conv2d):
+    """``torch.nn.Conv2d(cin, cout, 1, stride=2)`` with torch's constructor arguments and parameter names (``weight``, ``bias``:
+    ``state_dict``s interchange) whose forward is ``strided_conv1x1``.  An argument outside the supported family raises
+    ``NotImplementedError`` naming it."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=2, padding=0, dilation=1, groups=1, bias=True,
+                 padding_mode='zeros', device=None, dtype=None):
+        why = _strided_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels)
+        if why is not None:
+            raise NotImplementedError(why)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device, dtype)
+
+    def forward(self, x):
+        return strided_conv1x1(x, self.weight, self.bias)
+
+
+def _strided_why_not(conv):
+    if type(conv) is not torch.nn.Conv2d:
+        return f'a subclass of torch.nn.Conv2d ({type(conv).__name__}): its forward may differ'
+    if conv.weight.dtype not in _DTYPES:
+        return f'weight dtype {conv.weight.dtype}: float32 or bfloat16 only'
+    return _strided_unsupported(conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.padding_mode,
+                                conv.in_channels, conv.out_channels, conv.transposed)
+
+
+def _strided_from_torch(conv):
+    new = StridedConv1x1.__new__(StridedConv1x1)
+    new.__dict__.update(conv.__dict__)  # the same Parameter objects, hooks, training flag and constructor attributes
+    new._parameters = dict(conv._parameters)  # (the registry itself is the new module's own)
+    return new
+
+
+class Bottleneck(torch.nn.Module):
+    """The bottleneck block of a ResNet / ResNeXt encoder under torchvision's child names (``conv1``, ``bn1``, ``conv2``, ``bn2``,
+    ``conv3``, ``bn3``, ``relu``, ``downsample``: ``state_dict`` keys do not move), made of this module's pieces::
+
+        h, skip = conv1(x, fork=True)
+        h = bn1(h, activation='relu');  h = bn2(conv2(h), activation='relu');  h = conv3(h)
+        return bn3(h, residual=skip if downsample is None else downsample(skip), activation='relu')
+
+    ``conv1`` / ``conv3``: ``Conv2d`` (1x1); ``conv2``: ``GroupedConv2d`` or a 3x3 ``Conv2d``; the norms: ``BatchNorm2d``;
+    ``downsample``: None or ``Sequential(Conv2d | StridedConv1x1, BatchNorm2d)``.  ``relu`` is kept for its name only: the three
+    ReLUs run inside the norms.  Forward hooks on the children fire.  The output is saved by ``bn3``'s backward: an in-place
+    operation on it makes autograd raise."""
+
+    def __init__(self, conv1, bn1, conv2, bn2, conv3, bn3, downsample=None):
+        super().__init__()
+        self.conv1, self.bn1, self.conv2, self.bn2, self.conv3, self.bn3 = conv1, bn1, conv2, bn2, conv3, bn3
+        self.relu = torch.nn.ReLU(inplace=True)
+        self.downsample = downsample
+        why = _block_why_not(self, converted=True)
+        if why is not None:
+            raise NotImplementedError(why)
+
+    def forward(self, x):
+        h, skip = self.conv1(x, fork=True)
+        h = self.bn1(h, activation='relu')
+        h = self.bn2(self.conv2(h), activation='relu')
+        h = self.conv3(h)
+        return self.bn3(h, residual=skip if self.downsample is None else self.downsample(skip), activation='relu')
+
+
+_BLOCK_CHILDREN = ('conv1', 'bn1', 'conv2', 'bn2', 'conv3', 'bn3', 'relu', 'downsample')
+
+
+def _is_torchvision_bottleneck(cls):
+    """Whether the class's forward IS torchvision's ``Bottleneck.forward`` (told by its names: torchvision is not imported)."""
+    f = getattr(cls, 'forward', None)
+    return getattr(f, '__module__', None) == 'torchvision.models.resnet' and getattr(f, '__qualname__', None) == 'Bottleneck.forward'
+
+
+def _pointwise_why_not(conv, converted):
+    """conv1 / conv3: a 1x1 conv of ``conv2d``'s family."""
+    if isinstance(conv, Conv2d):
+        return None if _pair(conv.kernel_size) == (1, 1) else f'kernel_size {conv.kernel_size}: 1x1 only'
+    if converted or not isinstance(conv, torch.nn.Conv2d):
+        return f'{type(conv).__name__}: not a Conv2d of this library' if converted else f'{type(conv).__name__}: not a torch.nn.Conv2d'
+    if _pair(conv.kernel_size) != (1, 1):
+        return f'kernel_size {conv.kernel_size}: 1x1 only'
+    return _why_not(conv)
+
+
+def _conv2_why_not(conv, converted):
+    """conv2: ``grouped_conv2d``'s family (stride 1 or 2) or a dense 3x3 stride-1 conv of ``conv2d``'s."""
+    if isinstance(conv, GroupedConv2d):
+        return None
+    if isinstance(conv, Conv2d):
+        return None if _pair(conv.kernel_size) == (3, 3) else f'kernel_size {conv.kernel_size}: 3x3 only'
+    if converted or not isinstance(conv, torch.nn.Conv2d):
+        return f'{type(conv).__name__}: not a conv of this library' if converted else f'{type(conv).__name__}: not a torch.nn.Conv2d'
+    if _pair(conv.kernel_size) != (3, 3):
+        return f'kernel_size {conv.kernel_size}: 3x3 only'
+    return _grouped_why_not(conv) if conv.groups > 1 else _why_not(conv)
+
+
+def _norm_why_not(bn, converted):
+    if isinstance(bn, BatchNorm2d):
+        return None
+    if converted:
+        return f'{type(bn).__name__}: not a BatchNorm2d of this library'
+    return _bn_why_not(bn)
+
+
+def _shortcut_why_not(conv, converted):
+    """downsample.0: a 1x1 conv without padding, of stride 1 (``conv2d``'s family) or 2 (``strided_conv1x1``'s)."""
+    if isinstance(conv, StridedConv1x1):
+        return None
+    if isinstance(conv, Conv2d):
+        return None if _pair(conv.kernel_size) == (1, 1) else f'kernel_size {conv.kernel_size}: 1x1 only'
+    if converted or not isinstance(conv, torch.nn.Conv2d):
+        return f'{type(conv).__name__}: not a conv of this library' if converted else f'{type(conv).__name__}: not a torch.nn.Conv2d'
+    if _pair(conv.kernel_size) != (1, 1):
+        return f'kernel_size {conv.kernel_size}: 1x1 only'
+    return _strided_why_not(conv) if _pair(conv.stride) != (1, 1) else _why_not(conv)
+
+
+def _block_why_not(block, converted=False):
+    """The first child that keeps a block out of ``Bottleneck``, as ``'<attribute>: <reason>'``, or None.  ``converted``: the
+    children must be this library's modules already."""
+    for name in _BLOCK_CHILDREN:
+        if not hasattr(block, name):
+            return f'{name}: the block has no such attribute'
+    for name, check in (('conv1', _pointwise_why_not), ('bn1', _norm_why_not), ('conv2', _conv2_why_not), ('bn2', _norm_why_not),
+                        ('conv3', _pointwise_why_not), ('bn3', _norm_why_not)):
+        why = check(getattr(block, name), converted)
+        if why is not None:
+            return f'{name}: {why}'
+    if type(block.relu) is not torch.nn.ReLU:
+        return f'relu: {type(block.relu).__name__}: torch.nn.ReLU itself only'
+    down = block.downsample
+    if down is not None:
+        if type(down) is not torch.nn.Sequential or len(down) != 2:
+            inside = ', '.join(type(m).__name__ for m in down) if isinstance(down, torch.nn.Sequential) else type(down).__name__
+            return f'downsample: ({inside}): None or Sequential(1x1 conv, BatchNorm2d) only'
+        why = _shortcut_why_not(down[0], converted)
+        if why is not None:
+            return f'downsample.0: {why}'
+        why = _norm_why_not(down[1], converted)
+        if why is not None:
+            return f'downsample.1: {why}'
+    # the channel counts and the stride must fit together, or the residual add has no meaning
+    cin, mid, cout = block.conv1.in_channels, block.conv1.out_channels, block.conv3.out_channels
+    stride = _pair(block.conv2.stride)
+    if (block.conv2.in_channels, block.conv2.out_channels, block.conv3.in_channels) != (mid, mid, mid):
+        return f'conv2: {block.conv2.in_channels} -> {block.conv2.out_channels} channels between conv1 (-> {mid}) and conv3 ' \
+               f'({block.conv3.in_channels} ->)'
+    for name, bn, c in (('bn1', block.bn1, mid), ('bn2', block.bn2, mid), ('bn3', block.bn3, cout)):
+        if bn.num_features != c:
+            return f'{name}: num_features {bn.num_features} behind a conv of {c} channels'
+    if down is None:
+        if stride != (1, 1) or cin != cout:
+            return f'downsample: None with stride {stride} and {cin} -> {cout} channels: the identity shortcut needs stride 1 and ' \
+                   f'equal channel counts'
+    else:
+        if _pair(down[0].stride) != stride or (down[0].in_channels, down[0].out_channels) != (cin, cout) or down[1].num_features != cout:
+            return f'downsample.0: {down[0].in_channels} -> {down[0].out_channels} channels at stride {down[0].stride} beside a ' \
+                   f'block of {cin} -> {cout} channels at stride {stride}'
+    return None
+
+
+def _convert_child(child):
+    """A stock child of an eligible block -> this library's module sharing its Parameter and buffer objects."""
+    if isinstance(child, (Conv2d, GroupedConv2d, StridedConv1x1, BatchNorm2d)):
+        return child
+    if isinstance(child, torch.nn.BatchNorm2d):
+        return _bn_from_torch(child, None)
+    if child.groups > 1:
+        return _grouped_from_torch(child)
+    return _strided_from_torch(child) if _pair(child.stride) != (1, 1) else _from_torch(child)
+
+
+def _block_from_torch(block):
+    new = Bottleneck.__new__(Bottleneck)
+    new.__dict__.update(block.__dict__)  # hooks, training flag and the block's own attributes (stride, ...)
+    new._modules, new._parameters, new._buffers = dict(block._modules), dict(block._parameters), dict(block._buffers)
+    for name in ('conv1', 'bn1', 'conv2', 'bn2', 'conv3', 'bn3'):
+        setattr(new, name, _convert_child(getattr(block, name)))
+    if block.downsample is not None:  # the Sequential stays the object it is: its two slots are filled anew
+        block.downsample[0], block.downsample[1] = _convert_child(block.downsample[0]), _convert_child(block.downsample[1])
+    return new
+
+
+def convert_bottleneck_(module, block_types=()):
+    """Replaces every eligible bottleneck block below ``module`` in place by a ``Bottleneck`` -> (names replaced, {name left:
+    reason}).  A module is a candidate when its class's ``forward`` is torchvision's ``Bottleneck.forward`` (a class that assigns
+    that very function qualifies; one that merely has the same attribute names does not) or when its class is listed in
+    ``block_types``.  Eligible: ``conv1`` / ``conv3`` of ``conv2d``'s family, ``conv2`` of ``grouped_conv2d``'s (stride 1 or 2) or a
+    dense 3x3 stride-1 conv, the norms of ``batch_norm``'s, ``relu`` exactly ``torch.nn.ReLU``, ``downsample`` None or
+    ``Sequential(1x1 conv of stride 1 | 2 without padding, BatchNorm2d)``; the children may be stock or already converted by the
+    other converts, in any order: the result is the same, and ``Parameter`` and buffer objects are shared.  Everything else is left
+    with a reason naming the attribute; a block object that sits in two slots is left.  ``module`` itself is not replaced when it is
+    a candidate: it is reported as left.  The other converts, run afterwards, leave a converted block alone."""
+    block_types = tuple(block_types)
+    replaced, left = [], {}
+
+    def candidate(m):
+        return not isinstance(m, Bottleneck) and (_is_torchvision_bottleneck(type(m)) or type(m) in block_types)
+
+    if candidate(module):
+        left[''] = _block_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
+    uses = {}  # slots per candidate object in the whole tree: one that sits in two slots runs twice on different inputs
+    for parent in module.modules():
+        for child in parent._modules.values():
+            if child is not None and candidate(child):
+                uses[id(child)] = uses.get(id(child), 0) + 1
+    for name, parent in list(module.named_modules()):
+        for child_name, child in [(n, c) for n, c in parent._modules.items() if c is not None]:
+            if not candidate(child):
+                continue
+            full = f'{name}.{child_name}' if name else child_name
+            why = _block_why_not(child)
+            if why is None and uses[id(child)] > 1:
+                why = f'the block sits in {uses[id(child)]} slots'
+            if why is not None:
+                left[full] = why
+                continue
+            setattr(parent, child_name, _block_from_torch(child))
             replaced.append(full)
     return replaced, left

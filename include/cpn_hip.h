@@ -1202,6 +1202,44 @@ int cpn_grouped_conv_wgrad(const void *x, const void *dz, const void *dy, int32_
                            int32_t stride, int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db, int32_t db_dtype,
                            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Trainable bottleneck block -----------------------------------------------------------------------------
+ * What celldetection_amd.nn.Bottleneck needs besides the four sections above to run a ResNeXt bottleneck block, residual add and
+ * strided shortcut included (csrc/batch_norm.hip, csrc/grouped_conv_train.hip, csrc/grouped_conv.h).  Additions to ABI 22.  This
+ * text is the contract.
+ *
+ * A. Norm + residual add (+ ReLU): y = relu(bn(x) + r).  Layout, partition, dtype codes, alignment and limits are those of the
+ * "Trainable batch normalisation" section; r, y and g are [M][C] of x's dtype.
+ *   cpn_residual_bn_apply: t = fmaf(x, scale, shift) in fp32 with x widened exactly; s = t + r, an fp32 add with r widened exactly
+ *   (a rounding of its own: two roundings in fp32); y = s, or for relu != 0: s > 0 ? s : 0; a bf16 y is rounded once to nearest
+ *   even.  Three passes over the tensor: read x, read r, write y.
+ *   Backward.  The mask comes from the stored output: g = dy where y > 0 (in the stored dtype) and 0 elsewhere; r is not needed.
+ *   cpn_residual_bn_backward_reduce, relu != 0: reads x, dy and y, writes g once -- g IS the residual's gradient, bit for bit --
+ *   and accumulates sum g and sum g x in fp64 in the order and the workspace layout of cpn_bn_backward_reduce; the same finalising
+ *   kernel gives dgamma, dbeta and coeffs (all three NULL: g alone is written).  scale and shift are not read.  relu == 0: g = dy,
+ *   y and g are not looked at and nothing is written to g: the call is cpn_bn_backward_reduce with relu = 0.
+ *   cpn_bn_backward_input with relu = 0 on g then gives dx.  Passes backward: 4 + 3 = 7.
+ *
+ * B. Strided 1x1 shortcut conv, stride 2, no padding.  The forward is cpn_conv2d with kh = kw = 1, pad 0, stride 2 on x itself
+ * (the pointwise kernel gathers only its outputs): y [N][Hout][Wout][cout], Hout = (Hin - 1) / 2 + 1.  Input gradient: the
+ * stride-1 1x1 dgrad conv of dy at the output's size, then cpn_grouped_conv_dilate to the input's size (the even grid, exact zeros
+ * elsewhere).  Weight gradient: dw[o][c] = sum dy[i][j][o] x[2 i][2 j][c] = cpn_conv_wgrad(xs, dy, k = 1) with
+ *   cpn_subsample2d: xs [N][Hout][Wout][C], xs[n][i][j] = x[n][stride i][stride j], bf16 NHWC, 16 bytes per lane, every unit of xs
+ *   written once, for even and odd Hin / Win.  C a positive multiple of 8, stride 2, N, Hin, Win >= 1 (CPN_E_INVALID otherwise);
+ *   N * Hin * Win <= 2^31 - 1 and N * Hin * Win * C < 2^30 (CPN_E_UNSUPPORTED above); x and xs start at 16-byte aligned addresses
+ *   (CPN_E_INVALID).  It validates before it touches a pointer.
+ *
+ * C. Block-input gradient: the sum of the gradients of conv1's input and of the skip is the residual operand of the dgrad conv --
+ * cpn_conv2d with res = dskip, res_stride = cin: dx = round_bf16(fp32 conv sum + dskip), one rounding.  No entry point of its own.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_residual_bn_apply(const void *x, const void *r, void *y, int32_t dtype, int64_t M, int64_t C, int64_t slab_pixels,
+                          const float *scale, const float *shift, int32_t relu, void *stream);
+int cpn_residual_bn_backward_reduce(const void *x, const void *dy, const void *y, void *g, int32_t dtype, int64_t M, int64_t C,
+                                    int64_t slab_pixels, const float *scale, const float *shift, int32_t relu,
+                                    const float *save_mean, const float *save_invstd, const void *weight, int32_t weight_dtype,
+                                    void *dgamma, int32_t dgamma_dtype, void *dbeta, int32_t dbeta_dtype, float *coeffs,
+                                    void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_subsample2d(const void *x, int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t stride, void *xs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
