@@ -273,6 +273,16 @@ _SIGNATURES = [
                                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                                        c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     ('cpn_subsample2d', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_conv2d_sized', ctypes.c_int, [POINTER(OpDesc), c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                        c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    ('cpn_cat_conv_wgrad_workspace_bytes', c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                     c_int32]),
+    ('cpn_cat_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                               c_int32, POINTER(c_int32)]),
+    ('cpn_cat_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
+                                          c_void_p]),
+    ('cpn_nearest_sum', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -58,6 +58,9 @@ SOURCES = {
     # trainable grouped 3x3 conv: block-diagonal packs, stride-2 dilation, the weight gradient of the diagonal fragments (index
     # arithmetic: csrc/grouped_conv.h; the bias gradient's kernels: csrc/wgrad_bias.h)
     'grouped_conv_train.hip': [],
+    # trainable concat conv of the decoder: the weight gradient over the virtual concat of the lateral and the nearest-resized top,
+    # and the adjoint of the resize (index arithmetic: csrc/nearest_adjoint.h)
+    'cat_conv_train.hip': [],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -66,7 +69,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'grouped_conv.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -29,11 +29,11 @@ int check_hip(hipError_t e, const char *where) {
 // placeholder buffers: nothing here dereferences one)
 static int conv2d_args(const cpn_op_desc *op, const void *src0, int c0_stride, const void *src1, int c1_stride, const void *res,
                        int res_stride, void *dst, int dst_stride, int N, int Hin, int Win, const void *weights, const float *bias,
-                       ConvArgs &a) {
+                       ConvArgs &a, const int *stored = nullptr) {
     if (!op || !src0 || !dst || !weights) return fail(CPN_E_INVALID, "cpn_conv2d: null pointer");
     ConvBinding b;
     b.weights = weights; b.bias = bias;
-    return build_conv_args(b, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, Hin, Win);
+    return build_conv_args(b, *op, N, a, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, Hin, Win, stored);
 }
 
 static int conv2d_fp8_args(const cpn_op_desc *op, const void *src0, int c0_stride, const void *src1, int c1_stride,
@@ -322,6 +322,19 @@ int cpn_conv2d(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const
     int rc = conv2d_args(op, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, N, Hin, Win, weights, bias, a);
     if (rc) return rc;
     return check_hip((hipError_t) launch_conv(a, (hipStream_t) stream), "cpn_conv2d");
+}
+
+int cpn_conv2d_sized(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const void *src1, int32_t c1_stride,
+                     const void *res, int32_t res_stride, void *dst, int32_t dst_stride, int32_t N, int32_t Hin, int32_t Win,
+                     const int32_t stored[6], const void *weights, const float *bias, void *stream) {
+    if (!stored) return fail(CPN_E_INVALID, "cpn_conv2d_sized: null pointer");
+    if (op && ((op->up0 && (stored[0] < 1 || stored[1] < 1 || stored[0] > Hin || stored[1] > Win)) ||
+               (op->up1 && src1 && (stored[2] < 1 || stored[3] < 1 || stored[2] > Hin || stored[3] > Win))))
+        return fail(CPN_E_INVALID, "cpn_conv2d_sized: a resized source holds 1 ... Hin x 1 ... Win pixels");
+    ConvArgs a;
+    int rc = conv2d_args(op, src0, c0_stride, src1, c1_stride, res, res_stride, dst, dst_stride, N, Hin, Win, weights, bias, a, stored);
+    if (rc) return rc;
+    return check_hip((hipError_t) launch_conv(a, (hipStream_t) stream), "cpn_conv2d_sized");
 }
 
 int cpn_conv2d_fp8(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const void *src1, int32_t c1_stride,

@@ -17,7 +17,7 @@ Supported: ``groups = 1``, ``stride = 1``, ``dilation = 1``, a square odd ``k`` 
 ``Cin`` and ``Cout`` multiples of 32, a 4-D input on the GPU.  Everything else raises ``NotImplementedError`` naming the argument;
 there is no CPU fallback.  ``convert_conv2d_`` leaves every other conv and says why: the grouped 3x3 convs of the encoder are the
 business of ``grouped_conv2d``, the final 1x1 convs of the heads (1 / 2 / 20 output channels) of ``dropout_conv1x1``, both below.
-Known limit: the stem, the max-pool and the nearest resize with concat in the decoder stay stock torch operations.
+Known limit: the stem and the max-pool stay stock torch operations (the decoder's nearest resize with concat: ``cat_conv2d`` below).
 
 Arithmetic: activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32, the forward output
 and the input gradient are stored as bf16, the weight and bias gradients are fp32 sums rounded once to the parameter's dtype.  ``x``
@@ -43,9 +43,18 @@ dense stride-1 convs that ``convert_conv2d_`` takes.
 The whole bottleneck block runs here: ``Bottleneck`` and ``convert_bottleneck_`` (last part of this module; the rule is the
 "Trainable bottleneck block" section of include/cpn_hip.h) put the convs and norms above together with the norm's residual tail
 (``batch_norm(..., residual=)``: ``relu(bn3(h) + identity)`` in one pass), the strided 1x1 shortcut of a stage entry
-(``strided_conv1x1``) and the block-input gradient in the epilogue of ``conv1``'s input-gradient conv (``conv2d_fork``).  Known limits:
-at a stage entry the shortcut's norm and the tail are two kernels (``relu(bn3(h) + bn_d(h_d))`` is not one pass); the stem, the
-max-pool, the decoder's resize + concat and the bilinear resize behind the heads stay stock; ``cda.models.*`` stay inference-only.
+(``strided_conv1x1``) and the block-input gradient in the epilogue of ``conv1``'s input-gradient conv (``conv2d_fork``).  Known limit:
+at a stage entry the shortcut's norm and the tail are two kernels (``relu(bn3(h) + bn_d(h_d))`` is not one pass).
+
+The decoder's nearest resize + concat run here too: ``cat_conv2d`` (one ``torch.autograd.Function``: the conv reads the lateral and
+the low-resolution top through the loader's own nearest map, the weight gradient gathers the same way, the top's gradient goes
+through the exact adjoint of the resize, ``nearest_resize_backward``; neither the resized nor the concatenated tensor is written or
+saved), the ``nn.Conv2d`` drop-in ``CatConv2d``, the decoder ``UNetDecoder``, which also runs the level's 1x1 ``inner`` conv before
+the resize instead of after it, and ``convert_unet_decoder_`` (the part after the bottleneck; the rule is the "Trainable concat
+convolution" section of include/cpn_hip.h).  After it a decoder level runs conv -> norm -> ReLU -> conv -> norm -> ReLU on
+``(lateral, top)`` without a stock op.  Known limits: the top's gradient at the lateral's size is written once before it is summed
+(no footprint sum in the dgrad epilogue, no 4x4 stride-2 adjoint for the exact x2); the forward is not decomposed into sub-pixel
+phases; the stem, the max-pool and the bilinear resize behind the heads stay stock; ``cda.models.*`` stay inference-only.
 """
 import ctypes
 
@@ -59,7 +68,9 @@ __all__ = ['conv2d', 'Conv2d', 'convert_conv2d_', 'is_supported', 'pack_weight',
            'dropout_conv1x1', 'dropout_conv1x1_backward', 'readout_tail_info', 'DropoutConv1x1', 'convert_readout_tail_',
            'grouped_conv2d', 'GroupedConv2d', 'convert_grouped_conv2d_', 'grouped_weight_grad_info', 'grouped_conv2d_weight_grad',
            'grouped_pack_weight', 'grouped_dilate',
-           'conv2d_fork', 'strided_conv1x1', 'StridedConv1x1', 'subsample2d', 'Bottleneck', 'convert_bottleneck_']
+           'conv2d_fork', 'strided_conv1x1', 'StridedConv1x1', 'subsample2d', 'Bottleneck', 'convert_bottleneck_',
+           'cat_conv2d', 'CatConv2d', 'cat_conv2d_weight_grad', 'cat_weight_grad_info', 'nearest_resize_backward', 'UNetDecoder',
+           'convert_unet_decoder_']
 
 KERNEL_SIZES = (1, 3, 5, 7)
 _DTYPES = {torch.float32: _lib.CONV_TRAIN_F32, torch.bfloat16: _lib.CONV_TRAIN_BF16}
@@ -345,12 +356,12 @@ def convert_conv2d_(module):
     (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).  ``module`` itself is not replaced
     when it is a conv: it is reported as left."""
     replaced, left = [], {}
-    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, StridedConv1x1)):
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, StridedConv1x1, CatConv2d)):
         left[''] = _why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     for name, parent in list(module.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f'{name}.{child_name}' if name else child_name
-            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1)) or \
+            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d)) or \
                     not isinstance(child, torch.nn.modules.conv._ConvNd):
                 continue
             why = _why_not(child) if isinstance(child, torch.nn.Conv2d) else f'{type(child).__name__}: 2-D convs only'
@@ -926,7 +937,7 @@ def convert_readout_tail_(module):
         for child in parent._modules.values():
             if type(child) in (torch.nn.Dropout2d, torch.nn.Conv2d):
                 uses[id(child)] = uses.get(id(child), 0) + 1
-    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, DropoutConv1x1, StridedConv1x1)) and \
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, DropoutConv1x1, StridedConv1x1, CatConv2d)) and \
             _pair(module.kernel_size) == (1, 1):
         left[''] = _tail_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
@@ -934,7 +945,7 @@ def convert_readout_tail_(module):
         slots = [(n, c) for n, c in parent._modules.items() if c is not None]  # (named_children() drops repeated objects)
         for i, (child_name, child) in enumerate(slots):
             full = f'{name}.{child_name}' if name else child_name
-            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, (Conv2d, DropoutConv1x1, StridedConv1x1)) or \
+            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, (Conv2d, DropoutConv1x1, StridedConv1x1, CatConv2d)) or \
                     _pair(child.kernel_size) != (1, 1):
                 continue
             why = _tail_why_not(child)
@@ -1212,7 +1223,7 @@ def convert_grouped_conv2d_(module):
     when it is such a conv: it is reported as left.  A conv object that sits in several slots is replaced by one object in all of
     them.  Works before or after the other converts."""
     replaced, left = [], {}
-    ours = (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1)
+    ours = (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d)
     if isinstance(module, torch.nn.Conv2d) and not isinstance(module, ours) and module.groups > 1:
         left[''] = _grouped_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
@@ -1560,5 +1571,455 @@ def convert_bottleneck_(module, block_types=()):
                 left[full] = why
                 continue
             setattr(parent, child_name, _block_from_torch(child))
+            replaced.append(full)
+    return replaced, left
+
+
+# ---- the first conv of a U-Net decoder level: nearest resize + concat + conv ("Trainable concat convolution" of
+# include/cpn_hip.h, csrc/cat_conv_train.hip, csrc/nearest_adjoint.h)
+#
+# Every level of the reference decoder runs its block on ``cat((lateral, interpolate(top, size=lateral.shape[2:])), 1)``.  Stock torch
+# writes the resized and the concatenated tensor and saves the latter; ``cat_conv2d`` reads both sources in the conv's loader and in
+# the weight gradient's staging, and saves the lateral and the low-resolution top only.  The input gradient is two dgrad convs
+# (one per source, each run only when asked for); the top's goes through the adjoint of the resize, ``nearest_resize_backward``.
+# ``UNetDecoder`` also applies the level's 1x1 ``inner`` conv BEFORE the resize (per pixel the same bits, at the low resolution).
+# Known limits: the top's gradient at the lateral's size (``T``) is written and read once; the forward is not decomposed into
+# sub-pixel phases.
+
+CAT_KERNEL_SIZES = (1, 3, 5, 7)
+
+
+def _cat_channels(c0, c1, cout, k):
+    """Raises NotImplementedError naming the argument the concat conv does not run (``c0`` None: the bridge level)."""
+    if k not in CAT_KERNEL_SIZES:
+        raise NotImplementedError(f'kernel_size {k}: the concat conv runs square odd kernels {CAT_KERNEL_SIZES} only')
+    if c0 is not None and (c0 < 32 or c0 % 32):
+        raise NotImplementedError(f'lateral of {c0} channels: the concat conv needs a positive multiple of 32')
+    if c1 < 32 or c1 % 32:
+        raise NotImplementedError(f'top of {c1} channels: the concat conv needs a positive multiple of 32')
+    if cout < 32 or cout % 32:
+        raise NotImplementedError(f'out_channels {cout}: the concat conv needs a positive multiple of 32')
+
+
+def _check_cat(lateral, top, weight, bias):
+    """Raises for a call ``cat_conv2d`` does not run -> (N, C0 (0: bridge), C1, Cout, k, H, W, h, w)."""
+    if not isinstance(top, torch.Tensor) or top.dim() != 4:
+        raise NotImplementedError(f'top of {getattr(top, "dim", lambda: None)()} dimensions: the concat conv takes a 4-D [N, C1, h, w] top')
+    if lateral is not None and (not isinstance(lateral, torch.Tensor) or lateral.dim() != 4):
+        raise NotImplementedError(f'lateral of {getattr(lateral, "dim", lambda: None)()} dimensions: the concat conv takes a 4-D '
+                                  f'[N, C0, H, W] lateral or None')
+    if weight.dim() != 4:
+        raise NotImplementedError(f'weight of {weight.dim()} dimensions: the concat conv needs [Cout, C0 + C1, k, k]')
+    if weight.shape[2] != weight.shape[3]:
+        raise NotImplementedError(f'kernel_size {tuple(weight.shape[2:])}: the concat conv runs square kernels only')
+    if weight.dtype not in _DTYPES:
+        raise NotImplementedError(f'weight dtype {weight.dtype}: the concat conv takes float32 or bfloat16 parameters')
+    for name, t in (('top', top), ('lateral', lateral)):
+        if t is not None and t.dtype not in _DTYPES:
+            raise NotImplementedError(f'{name} dtype {t.dtype}: the concat conv takes float32 or bfloat16 activations')
+    n, c1, h, w = (int(v) for v in top.shape)
+    cout, cin, k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+    c0 = None if lateral is None else int(lateral.shape[1])
+    _cat_channels(c0, c1, cout, k)
+    if (c0 or 0) + c1 != cin:
+        raise ValueError(f'lateral and top have {c0 or 0} + {c1} channels, weight expects {cin}')
+    if lateral is None:
+        H, W = 2 * h, 2 * w
+    else:
+        H, W = int(lateral.shape[2]), int(lateral.shape[3])
+        if int(lateral.shape[0]) != n:
+            raise ValueError(f'lateral holds {int(lateral.shape[0])} images, top {n}')
+        if h > H or w > W:
+            raise NotImplementedError(f'top of {h} x {w} pixels is larger than the lateral of {H} x {W}: the concat conv resizes upwards '
+                                      f'only')
+    if n * h * w == 0 or n * H * W == 0:
+        raise NotImplementedError(f'top of shape {tuple(top.shape)}' + (f', lateral of shape {tuple(lateral.shape)}' if lateral is not None
+                                                                          else '') + ': the concat conv needs at least one pixel')
+    if bias is not None and (bias.dim() != 1 or int(bias.shape[0]) != cout or bias.dtype not in _DTYPES):
+        raise NotImplementedError(f'bias {tuple(bias.shape)} {bias.dtype}: the concat conv takes a float32 or bfloat16 [{cout}] bias')
+    _need_cuda(lateral, top, weight, bias)
+    return n, c0 or 0, c1, cout, k, H, W, h, w
+
+
+def _cat_desc(c0, c1, cout, k, bias):
+    """cpn_op_desc of the concat conv: the lateral plain, the top resized by the loader; without a lateral the lone source resized."""
+    d = _conv_desc(c0 + c1, cout, k, bias)
+    if c0:
+        d.src1, d.up1, d.c0_used = 2, 1, c0
+    else:
+        d.up0 = 1
+    return d
+
+
+def _run_cat_conv(ls, ts, packed, bias, c0, c1, cout, k, size):
+    """ls: bf16 NHWC memory [N, C0, H, W] or None, ts: [N, C1, h, w] -> bf16 [N, cout, H, W] in channels_last: ``cpn_conv2d_sized``
+    on the two sources (``cpn_conv2d`` on the lone resized source of the bridge level)."""
+    n, _, h, w = (int(v) for v in ts.shape)
+    H, W = size
+    out = torch.empty((n, cout, H, W), dtype=torch.bfloat16, device=ts.device, memory_format=torch.channels_last)
+    d = _cat_desc(c0, c1, cout, k, bias is not None)
+    lib = _lib.load()
+    if ls is None:
+        assert (H, W) == (2 * h, 2 * w), (H, W, h, w)
+        _lib.check(lib.cpn_conv2d(ctypes.byref(d), _lib.ptr(ts), c1, _lib.ptr(None), 0, _lib.ptr(None), 0, _lib.ptr(out), cout, n, H, W,
+                                  _lib.ptr(packed), _lib.ptr(bias), _lib.stream_ptr()), 'cat_conv2d')
+    else:
+        stored = (ctypes.c_int32 * 6)(H, W, h, w, H, W)
+        _lib.check(lib.cpn_conv2d_sized(ctypes.byref(d), _lib.ptr(ls), c0, _lib.ptr(ts), c1, _lib.ptr(None), 0, _lib.ptr(out), cout, n,
+                                        H, W, stored, _lib.ptr(packed), _lib.ptr(bias), _lib.stream_ptr()), 'cat_conv2d')
+    return out
+
+
+def cat_weight_grad_info(n, h, w, c0, c1, top_size, cout, k, slab_rows=0):
+    """What ``cat_conv2d_weight_grad`` would run on ``n`` laterals of ``h`` x ``w`` (``c0`` = 0: the bridge level) and tops of
+    ``top_size`` -> dict(slabs, slab_rows, steps (MFMA steps per slab), reduce_chain, bias_chain).  Host arithmetic only: needs no GPU.
+    Raises like the launch for a call it rejects."""
+    info = (ctypes.c_int32 * 5)()
+    _lib.check(_lib.load().cpn_cat_conv_wgrad_info(n, h, w, c0, c1, int(top_size[0]), int(top_size[1]), cout, k, slab_rows, info),
+               'cat_conv_wgrad_info')
+    return dict(zip(('slabs', 'slab_rows', 'steps', 'reduce_chain', 'bias_chain'), (int(v) for v in info)))
+
+
+def cat_conv2d_weight_grad(lateral, top, grad_output, kernel_size, slab_rows=0, weight=True, bias=True, dtype=torch.float32,
+                           bias_dtype=None):
+    """(lateral [N, C0, H, W] | None, top [N, C1, h, w], grad_output [N, Cout, H, W]) -> (dW [Cout, C0 + C1, k, k] | None, db [Cout] |
+    None): the gradients ``cat_conv2d`` returns for its weight and bias, as fp32 sums over the bf16-rounded operands of the virtual
+    concat rounded once to ``dtype`` / ``bias_dtype``.  ``slab_rows``: image rows per slab of the reduction (0: chosen by the library)."""
+    _need_cuda(lateral, top, grad_output)
+    k = int(kernel_size)
+    n, c1, h1, w1 = (int(v) for v in top.shape)
+    c0 = 0 if lateral is None else int(lateral.shape[1])
+    cout, h, w = int(grad_output.shape[1]), int(grad_output.shape[2]), int(grad_output.shape[3])
+    _cat_channels(None if lateral is None else c0, c1, cout, k)
+    bias_dtype = dtype if bias_dtype is None else bias_dtype
+    if dtype not in _DTYPES or bias_dtype not in _DTYPES:
+        raise NotImplementedError(f'dtype {dtype} / {bias_dtype}: gradients are float32 or bfloat16')
+    assert int(grad_output.shape[0]) == n and (lateral is None or tuple(lateral.shape) == (n, c0, h, w)) and \
+        (lateral is not None or (h, w) == (2 * h1, 2 * w1)), (tuple(grad_output.shape), tuple(top.shape))
+    if not (weight or bias):
+        return None, None
+    dw = torch.empty((cout, c0 + c1, k, k), dtype=dtype, device=top.device) if weight else None
+    db = torch.empty((cout,), dtype=bias_dtype, device=top.device) if bias else None
+    ls = None if lateral is None else _nhwc(lateral, torch.bfloat16)
+    ts, gs = _nhwc(top, torch.bfloat16), _nhwc(grad_output, torch.bfloat16)
+    lib = _lib.load()
+    nbytes = int(lib.cpn_cat_conv_wgrad_workspace_bytes(n, h, w, c0, c1, h1, w1, cout, k, slab_rows))
+    if nbytes <= 0:
+        _lib.check(lib.cpn_cat_conv_wgrad_info(n, h, w, c0, c1, h1, w1, cout, k, slab_rows, (ctypes.c_int32 * 5)()), 'cat_conv_wgrad')
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=top.device)
+    _lib.check(lib.cpn_cat_conv_wgrad(_lib.ptr(ls), _lib.ptr(ts), _lib.ptr(gs), n, h, w, c0, c1, h1, w1, cout, k, slab_rows, _lib.ptr(dw),
+                                      _DTYPES[dtype], _lib.ptr(db), _DTYPES[bias_dtype], _lib.ptr(ws), nbytes, _lib.stream_ptr()),
+               'cat_conv_wgrad')
+    return dw, db
+
+
+def nearest_resize_backward(t, size):
+    """The adjoint of ``F.interpolate(x, size=t.shape[2:], mode='nearest')`` for ``x`` of ``size`` = (h, w): t [N, C, H, W] -> bf16
+    [N, C, h, w] in ``torch.channels_last``, every pixel the sum of ``t`` over the pixels that read it (fp32 adds in ascending
+    row-major order, one rounding; exact zeros where none does).  ``t`` is rounded to bf16 on the way in; ``C`` a positive multiple
+    of 8, 1 <= h <= H, 1 <= w <= W.  Known limit: one lane walks a pixel's whole footprint, which suits the 2 x 2 footprints of a
+    decoder; any ratio is correct, but a tiny ``size`` under a large ``t`` leaves a few lanes reading the whole image."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise NotImplementedError(f'input of {getattr(t, "dim", lambda: None)()} dimensions: the resize adjoint takes a 4-D [N, C, H, W] input')
+    if t.dtype not in _DTYPES:
+        raise NotImplementedError(f'input dtype {t.dtype}: the resize adjoint takes float32 or bfloat16 activations')
+    n, c, H, W = (int(v) for v in t.shape)
+    h, w = (int(v) for v in size)
+    if c < 8 or c % 8:
+        raise NotImplementedError(f'input of {c} channels: the resize adjoint needs a positive multiple of 8')
+    if h < 1 or w < 1 or h > H or w > W or n < 1:
+        raise NotImplementedError(f'size {(h, w)} for an input of shape {tuple(t.shape)}: the resize adjoint needs 1 <= h <= H and '
+                                  f'1 <= w <= W and at least one image')
+    _need_cuda(t)
+    ts = _nhwc(t, torch.bfloat16)
+    out = torch.empty((n, c, h, w), dtype=torch.bfloat16, device=ts.device, memory_format=torch.channels_last)
+    _lib.check(_lib.load().cpn_nearest_sum(_lib.ptr(ts), n, H, W, c, _lib.ptr(out), h, w, _lib.stream_ptr()), 'nearest_sum')
+    return out
+
+
+class _CatConv2dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lateral, top, weight, bias):
+        cout, k = int(weight.shape[0]), int(weight.shape[2])
+        c1 = int(top.shape[1])
+        c0 = int(weight.shape[1]) - c1
+        ls = None if lateral is None else _nhwc(lateral, torch.bfloat16)
+        ts = _nhwc(top, torch.bfloat16)
+        size = (2 * int(top.shape[2]), 2 * int(top.shape[3])) if lateral is None else (int(lateral.shape[2]), int(lateral.shape[3]))
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        out = _run_cat_conv(ls, ts, pack_weight(weight, 'forward'), b32, c0, c1, cout, k, size)
+        ctx.save_for_backward(ls, ts, weight)  # the lateral and the top at its own low resolution: nothing of the concat's size
+        ctx.lateral_dtype = None if lateral is None else lateral.dtype
+        ctx.top_dtype = top.dtype
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        ls, ts, weight = ctx.saved_tensors
+        cout, k = int(weight.shape[0]), int(weight.shape[2])
+        c1 = int(ts.shape[1])
+        c0 = int(weight.shape[1]) - c1
+        need_l, need_t, need_w, need_b = ctx.needs_input_grad
+        need_l = need_l and ls is not None
+        need_b = need_b and ctx.bias_dtype is not None
+        gs = _nhwc(grad_output, torch.bfloat16)
+        dl = dt = dw = db = None
+        if need_l:  # dcat[:, :C0]: the dgrad conv on the lateral's part of the weights, written directly
+            dl = _run_conv(gs, pack_weight(weight.detach()[:, :c0], 'dgrad'), None, cout, c0, k).to(ctx.lateral_dtype)
+        if need_t:  # T = dcat[:, C0:] at the lateral's size, then the footprint sums (the identity resize: T itself)
+            t = _run_conv(gs, pack_weight(weight.detach()[:, c0:], 'dgrad'), None, cout, c1, k)
+            dt = (t if t.shape[2:] == ts.shape[2:] else nearest_resize_backward(t, ts.shape[2:])).to(ctx.top_dtype)
+        if need_w or need_b:
+            dw, db = cat_conv2d_weight_grad(ls, ts, gs, k, weight=need_w, bias=need_b, dtype=weight.dtype,
+                                            bias_dtype=ctx.bias_dtype or weight.dtype)
+        return dl, dt, dw, db
+
+
+def cat_conv2d(lateral, top, weight, bias=None):
+    """``F.conv2d(torch.cat((lateral, F.interpolate(top, size=lateral.shape[2:], mode='nearest')), 1), weight, bias, padding=k // 2)``
+    -- the lateral first -- as one autograd function that never writes the resized or the concatenated tensor, with gradients for
+    ``lateral``, ``top``, ``weight`` and ``bias`` as autograd asks for them -> bf16 ``[N, Cout, H, W]`` in ``torch.channels_last``.
+
+    ``lateral`` ``[N, C0, H, W]``, ``top`` ``[N, C1, h, w]`` with 1 <= h <= H and 1 <= w <= W at any ratio (equal sizes: no resize),
+    ``weight`` ``[Cout, C0 + C1, k, k]``; ``lateral=None`` is the bridge level: the only source is ``top`` resized by exactly 2
+    (``scale_factor=2``) -> ``[N, Cout, 2h, 2w]``.  The family is ``conv2d``'s: ``C0``, ``C1`` and ``Cout`` positive multiples of 32,
+    a square odd ``k`` in {1, 3, 5, 7}, stride 1, zero padding ``k // 2``, float32 or bfloat16 inputs and parameters on the GPU.
+    Anything else raises ``NotImplementedError`` naming the argument; there is no fallback.
+
+    Arithmetic is ``conv2d``'s.  The lateral's gradient is written by its own dgrad conv; the top's is the dgrad conv at the lateral's
+    size followed by ``nearest_resize_backward``, whose index map is the forward loader's own, so the two are exact adjoints at every
+    size; a conv whose gradient is not asked for is not run.  Saved for backward: the bf16 lateral, the bf16 top at its low
+    resolution and ``weight``."""
+    _check_cat(lateral, top, weight, bias)
+    return _CatConv2dFunction.apply(lateral, top, weight, bias)
+
+
+_ONE_INPUT = object()  # CatConv2d.forward(x): the concatenated tensor itself
+
+
+class CatConv2d(torch.nn.Conv2d):
+    """``torch.nn.Conv2d`` with torch's constructor arguments and parameter names (``in_channels`` = C0 + C1; ``state_dict``s
+    interchange) at the head of a decoder level: ``forward(lateral, top)`` is ``cat_conv2d``, ``forward(None, top)`` the bridge level,
+    and ``forward(x)`` with the one concatenated tensor is ``conv2d(x)``, so the module keeps working inside a stock ``Sequential``.
+    ``padding`` defaults to ``kernel_size // 2``; an argument outside the supported family raises ``NotImplementedError`` naming it."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=None, dilation=1, groups=1, bias=True,
+                 padding_mode='zeros', device=None, dtype=None):
+        ks = _pair(kernel_size)
+        padding = ks[0] // 2 if padding is None else padding
+        why = _unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels)
+        if why is not None:
+            raise NotImplementedError(why)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device, dtype)
+
+    def forward(self, lateral, top=_ONE_INPUT):
+        if top is _ONE_INPUT:
+            return conv2d(lateral, self.weight, self.bias)
+        return cat_conv2d(lateral, top, self.weight, self.bias)
+
+
+def _cat_from_torch(conv):
+    new = CatConv2d.__new__(CatConv2d)
+    new.__dict__.update(conv.__dict__)  # the same Parameter objects, hooks, training flag and constructor attributes
+    new._parameters = dict(conv._parameters)  # (the registry itself is the new module's own)
+    return new
+
+
+def _is_reference_unet(cls):
+    """Whether the class's forward IS the reference's ``GeneralizedUNet.forward`` (told by its names: the reference is not imported)."""
+    f = getattr(cls, 'forward', None)
+    return getattr(f, '__module__', None) == 'celldetection.models.unet' and getattr(f, '__qualname__', None) == 'GeneralizedUNet.forward'
+
+
+_DECODER_FLAGS = ('block_cat', 'block_interpolate', 'bridge_block_interpolate')
+_DECODER_ATTRIBUTES = ('inner_blocks', 'layer_blocks', 'has_lat', 'bridges', 'interpolate', 'cat_order') + _DECODER_FLAGS + \
+    ('extra_blocks', 'out_layer', 'final_interpolate', 'final_activation', 'keep_features', 'features_prefix')
+
+
+def _slot0_why_not(conv, converted):
+    """Slot 0 of a layer block: a stride-1 conv of ``conv2d``'s family, stock or this library's."""
+    if isinstance(conv, (CatConv2d, Conv2d)):
+        return None if not converted or isinstance(conv, CatConv2d) else f'{type(conv).__name__}: not a CatConv2d'
+    if converted or not isinstance(conv, torch.nn.Conv2d):
+        return f'{type(conv).__name__}: not a CatConv2d' if converted else f'{type(conv).__name__}: not a torch.nn.Conv2d'
+    return _why_not(conv)
+
+
+def _decoder_why_not(dec, converted=False):
+    """The first attribute that keeps a decoder out of ``UNetDecoder``, as ``'<attribute>: <reason>'``, or None.  ``converted``:
+    slot 0 of every layer block must be a ``CatConv2d`` and every inner conv a ``Conv2d`` of this library already."""
+    for name in _DECODER_ATTRIBUTES:
+        if not hasattr(dec, name):
+            return f'{name}: the decoder has no such attribute'
+    if dec.interpolate != 'nearest':
+        return f"interpolate: {dec.interpolate!r}: 'nearest' only"
+    if dec.cat_order != 0:
+        return f'cat_order: {dec.cat_order}: 0 (the lateral first) only'
+    for name in _DECODER_FLAGS:
+        if getattr(dec, name):
+            return f'{name}: {getattr(dec, name)!r}: the block must not resize or concatenate itself'
+    if dec.extra_blocks is not None:
+        return f'extra_blocks: {type(dec.extra_blocks).__name__}: None only'
+    inner, layers = dec.inner_blocks, dec.layer_blocks
+    if not isinstance(inner, torch.nn.ModuleList) or not isinstance(layers, torch.nn.ModuleList) or len(inner) != len(layers) or \
+            len(layers) < 1:
+        return f'layer_blocks: {len(layers) if hasattr(layers, "__len__") else "?"} blocks beside ' \
+               f'{len(inner) if hasattr(inner, "__len__") else "?"} inner blocks: two ModuleLists of one length >= 1'
+    try:
+        [dec.has_lat[i] for i in range(len(layers))]
+    except (KeyError, IndexError, TypeError):
+        return f'has_lat: {dec.has_lat!r}: one entry per level 0 ... {len(layers) - 1}'
+    top_channels = None  # of the deepest level: the encoder's, not known here
+    for i in range(len(layers) - 1, -1, -1):
+        m = inner[i]
+        if type(m) is not torch.nn.Identity:
+            why = _pointwise_why_not(m, converted)
+            if why is not None:
+                return f'inner_blocks.{i}: {why}'
+            if top_channels is not None and m.in_channels != top_channels:
+                return f'inner_blocks.{i}: in_channels {m.in_channels} behind a level of {top_channels} channels'
+            top_channels = m.out_channels
+        block = layers[i]
+        # (the reference's TwoConvNormRelu IS such a subclass: nn.Sequential with a constructor and no forward of its own)
+        if not isinstance(block, torch.nn.Sequential) or type(block).forward is not torch.nn.Sequential.forward or len(block) < 1:
+            return f'layer_blocks.{i}: {type(block).__name__}: an nn.Sequential (or a subclass that keeps its forward) with the conv ' \
+                   f'in slot 0 only'
+        conv = block[0]
+        why = _slot0_why_not(conv, converted)
+        if why is not None:
+            return f'layer_blocks.{i}.0: {why}'
+        if top_channels is not None:
+            lateral = conv.in_channels - top_channels
+            if dec.has_lat[i] and (lateral < 32 or lateral % 32):
+                return f'layer_blocks.{i}.0: in_channels {conv.in_channels} = {lateral} lateral + {top_channels} top channels: the ' \
+                       f'lateral needs a positive multiple of 32'
+            if not dec.has_lat[i] and lateral != 0:
+                return f'layer_blocks.{i}.0: in_channels {conv.in_channels} on a bridge level whose top has {top_channels} channels'
+        elif dec.has_lat[i] and conv.in_channels < 64:
+            return f'layer_blocks.{i}.0: in_channels {conv.in_channels}: lateral + top need at least 32 + 32 channels'
+        outs = [m.out_channels for m in block if isinstance(m, torch.nn.modules.conv._ConvNd)]
+        top_channels = outs[-1]
+    return None
+
+
+class UNetDecoder(torch.nn.Module):
+    """The reference's ``GeneralizedUNet`` decoder (default path: nearest resize, the lateral first in the concat) on this library's
+    pieces, under the reference's child names ``inner_blocks`` and ``layer_blocks`` (``state_dict`` keys do not move)::
+
+        for i in levels, deepest first:
+            top  = inner_blocks[i](last)                                  # the 1x1 conv BEFORE the resize; Identity stays Identity
+            h    = layer_blocks[i][0](lateral if has_lat[i] else None, top)    # CatConv2d: resize + concat + conv in one function
+            last = layer_blocks[i][1:](h)                                 # the remaining slots, in order
+
+    The reference resizes first and applies the inner conv at the lateral's size; a 1x1 conv commutes with the nearest resize pixel
+    by pixel, so the values are the same at a quarter of the work.  The tail -- the final bilinear resize to ``size``, ``out_layer``,
+    ``final_activation``, the result dict with ``'out'`` and the ``encoder.*`` keys of ``keep_features`` -- is the reference's, in
+    stock torch ops.  ``has_lat``: per level, whether it has a lateral (False: a bridge level, resized by exactly 2);
+    ``bridges``: the number of bridge levels.  Forward hooks on a level's children (the convs, the norms) fire; hooks on a level's
+    ``Sequential`` itself do not, because its slots are called one by one."""
+
+    def __init__(self, inner_blocks, layer_blocks, has_lat, bridges=0, out_layer=None, final_activation=None,
+                 final_interpolate='bilinear', keep_features=True, features_prefix='encoder'):
+        super().__init__()
+        self.inner_blocks, self.layer_blocks = inner_blocks, layer_blocks
+        self.has_lat = dict(has_lat) if isinstance(has_lat, dict) else dict(enumerate(has_lat))
+        self.bridges = int(bridges)
+        self.interpolate, self.cat_order = 'nearest', 0
+        self.block_cat = self.block_interpolate = self.bridge_block_interpolate = False
+        self.extra_blocks = None
+        self.out_layer, self.final_activation, self.final_interpolate = out_layer, final_activation, final_interpolate
+        self.keep_features, self.features_prefix = keep_features, features_prefix
+        why = _decoder_why_not(self, converted=True)
+        if why is not None:
+            raise NotImplementedError(why)
+
+    @property
+    def depth(self):
+        return len(self.layer_blocks)
+
+    def forward(self, x, size=None):
+        features = x
+        names = list(x.keys())
+        x = list(x.values())
+        last = x[-1]
+        results = [last]
+        for i in range(len(self.layer_blocks) - 1, -1, -1):
+            lateral = x[i - self.bridges] if self.has_lat[i] else None
+            top = self.inner_blocks[i](last)
+            slots = list(self.layer_blocks[i])
+            last = slots[0](lateral, top)
+            for m in slots[1:]:
+                last = m(last)
+            results.insert(0, last)
+        if size is None:
+            final = results[0]
+        else:
+            final = torch.nn.functional.interpolate(last, size=size, mode=self.final_interpolate, align_corners=False)
+        if self.out_layer is not None:
+            final = self.out_layer(final)
+        if self.final_activation is not None:
+            final = self.final_activation(final)
+        if self.out_layer is not None:
+            return final
+        results.insert(0, final)
+        names.insert(0, 'out')
+        out = dict(zip(names, results))
+        if self.keep_features:
+            out.update(('.'.join([self.features_prefix, k]), v) for k, v in features.items())
+        return out
+
+
+def _decoder_from_torch(dec):
+    new = UNetDecoder.__new__(UNetDecoder)
+    new.__dict__.update(dec.__dict__)  # hooks, training flag and the decoder's own attributes (has_lat, bridges, out_channels, ...)
+    new._modules, new._parameters, new._buffers = dict(dec._modules), dict(dec._parameters), dict(dec._buffers)
+    for i, m in enumerate(dec.inner_blocks):  # the ModuleLists and Sequentials stay the objects they are: their slots are filled anew
+        if type(m) is torch.nn.Conv2d:
+            dec.inner_blocks[i] = _from_torch(m)
+    for block in dec.layer_blocks:
+        if not isinstance(block[0], CatConv2d):
+            block[0] = _cat_from_torch(block[0])
+    return new
+
+
+def convert_unet_decoder_(module, decoder_types=()):
+    """Replaces every eligible U-Net decoder below ``module`` in place by a ``UNetDecoder`` -> (names replaced, {name left:
+    reason}).  A module is a candidate when its class's ``forward`` is the reference's ``GeneralizedUNet.forward`` (told by the names
+    ``celldetection.models.unet`` / ``GeneralizedUNet.forward``; a class that merely has the same attributes does not qualify) or
+    when its class is listed in ``decoder_types``.  Eligible: ``interpolate == 'nearest'``, ``cat_order == 0``, ``block_cat``,
+    ``block_interpolate`` and ``bridge_block_interpolate`` all false, ``extra_blocks is None``, every inner block ``Identity`` or a
+    1x1 conv of ``conv2d``'s family, every layer block an ``nn.Sequential`` -- itself or a subclass that does not override ``forward``, as the reference's
+    ``TwoConvNormRelu`` is; its slots are called one by one -- whose slot 0 is a stride-1 conv of that family with
+    ``in_channels`` = lateral + top channels (= top on a bridge level).  Slot 0 becomes a ``CatConv2d`` and a stock inner conv a
+    ``Conv2d``, stock or already converted by the other converts, in any order: the result is the same, and ``Parameter`` objects are
+    shared.  Everything else is left with a reason naming the attribute; a decoder object that sits in two slots is left.
+    ``module`` itself is not replaced when it is a candidate: it is reported as left.  The other converts, run afterwards, take the
+    remaining slots of the levels and leave the ``CatConv2d`` alone."""
+    decoder_types = tuple(decoder_types)
+    replaced, left = [], {}
+
+    def candidate(m):
+        return not isinstance(m, UNetDecoder) and (_is_reference_unet(type(m)) or type(m) in decoder_types)
+
+    if candidate(module):
+        left[''] = _decoder_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
+    uses = {}
+    for parent in module.modules():
+        for child in parent._modules.values():
+            if child is not None and candidate(child):
+                uses[id(child)] = uses.get(id(child), 0) + 1
+    for name, parent in list(module.named_modules()):
+        for child_name, child in [(n, c) for n, c in parent._modules.items() if c is not None]:
+            if not candidate(child):
+                continue
+            full = f'{name}.{child_name}' if name else child_name
+            why = _decoder_why_not(child)
+            if why is None and uses[id(child)] > 1:
+                why = f'the decoder sits in {uses[id(child)]} slots'
+            if why is not None:
+                left[full] = why
+                continue
+            setattr(parent, child_name, _decoder_from_torch(child))
             replaced.append(full)
     return replaced, left

@@ -1240,6 +1240,73 @@ int cpn_residual_bn_backward_reduce(const void *x, const void *dy, const void *y
                                     void *workspace, int64_t workspace_bytes, void *stream);
 int cpn_subsample2d(const void *x, int32_t N, int32_t Hin, int32_t Win, int32_t C, int32_t stride, void *xs, void *stream);
 
+/* ---- Trainable concat convolution ---------------------------------------------------------------------------
+ * What celldetection_amd.nn.cat_conv2d needs besides cpn_conv2d and the "Trainable convolution" section to train the first conv
+ * of a U-Net decoder level (csrc/cat_conv_train.hip, csrc/nearest_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to
+ * ABI 22.  This text is the contract.
+ *
+ * The function.  y = conv(cat(x0, R(x1)), w) + b with x0 [N][H][W][C0] (the lateral) first and x1 [N][h][w][C1] (the top) second,
+ * 1 <= h <= H, 1 <= w <= W, bf16 NHWC; w [cout][C0 + C1][k][k], k square and odd, stride 1, padding k / 2 with zeros; C0, C1 and
+ * cout positive multiples of 32.  R is PyTorch's 'nearest' resize to H x W: R(x1)[n][y][x] = x1[n][src_y(y)][src_x(x)] with
+ * src(d) = min((int) floorf((float) d * scale), in - 1), scale = (float) in / (float) out -- nearest_src of csrc/cpn_kernels.h,
+ * restated as na_src in csrc/nearest_adjoint.h.  Equal sizes make R the identity.  The bridge level has no lateral: C0 = 0,
+ * x0 = NULL, and H = 2 h, W = 2 w exactly.
+ *
+ * Arithmetic.  Operands are rounded to bf16 (round to nearest even), sums are fp32, every stored value is rounded once.
+ *
+ * Forward.  cpn_conv2d_sized with src1 = x1, up1 = 1, c0_used = C0, cin_b = C0 + C1 on the forward pack of w (cpn_conv_train_pack):
+ * the loader resizes the second source; neither R(x1) nor the concatenated tensor is ever written.
+ *   cpn_conv2d_sized: cpn_conv2d plus stored[6] = {Hs0, Ws0, Hs1, Ws1, Hr, Wr}, the sizes at which the two sources and the residual
+ *   are stored (looked at for a source with up != 0 and a residual with res_up != 0 only; cpn_conv2d assumes Hin >> 1 x Win >> 1).
+ *   A resized source of less than 1 or more than Hin x Win pixels, or stored == NULL: CPN_E_INVALID before a pointer is read.
+ * The bridge level is cpn_conv2d with the lone source resized (up0 = 1: exactly x2).
+ *
+ * Input gradients.  dcat = the stride-1 conv of dY with the taps flipped and the channel roles swapped, as in the "Trainable
+ * convolution" section, run as two convs on the dgrad packs of w[:, :C0] and w[:, C0:]:
+ *   d_x0 = dcat[:, :C0], written directly, one rounding;
+ *   T = dcat[:, C0:], bf16 at the lateral's size [N][H][W][C1];
+ *   d_x1[n][i][j][c] = the sum of T[n][y][x][c] over all (y, x) with src_y(y) = i and src_x(x) = j (the footprint of (i, j)), the
+ *   adds in fp32 in ascending row-major (y, x) order, rounded once to bf16; an empty footprint gives an exact zero.  src is the
+ *   function of the forward, so forward and backward are exact adjoints at every size.  src is non-decreasing: a footprint is the
+ *   product of two contiguous ranges, [na_first(i), na_first(i + 1)) per axis.
+ *   cpn_nearest_sum: d_x1 from T.  16 bytes (8 channels) per lane; C a positive multiple of 8, N, H, W >= 1, 1 <= h <= H,
+ *   1 <= w <= W (CPN_E_INVALID otherwise), N * H * W <= 2^31 - 1 (CPN_E_UNSUPPORTED above), t and dst 16-byte aligned.
+ * A conv whose gradient is not asked for is not run.
+ *
+ * Weight and bias gradients.  dw[co][ci][ky][kx] = sum over pixels p of dY[p][co] * X[p + (ky - pad) * W + (kx - pad)][ci] with
+ * zeros outside the image, where X is the VIRTUAL concat: channels ci < C0 come from x0 at the pixel, channels ci >= C0 from x1 at
+ * the pixel's source pixel.  Partition, chains and rounding are those of cpn_conv_wgrad: slabs of slab_rows image rows of the
+ * N * H rows, 16 pixels per MFMA step in one fp32 accumulator per output, then the slabs' partial sums added in ascending slab
+ * order (+ one add per slab), rounded once to dw_dtype; db likewise from dY alone.  No floating-point atomics: bit-identical from
+ * run to run.  A 32-channel block of the 64-channel tile belongs to one source; the source pixel of each staged row is computed
+ * once per 128-pixel chunk into an LDS table; R(x1) is never materialised.
+ *   cpn_cat_conv_wgrad_info / cpn_cat_conv_wgrad_workspace_bytes / cpn_cat_conv_wgrad: the argument order of cpn_conv_wgrad_info /
+ *   _workspace_bytes / cpn_conv_wgrad with (x0, x1) in place of x and (c0, c1, h1, w1) in place of cin.  info[5] = {slabs,
+ *   slab_rows, MFMA steps of the largest slab, reduce chain, bias chain}; the chain of one dw element is info[2] + 2 + info[3].
+ *   c0 = 0 with x0 = NULL is the bridge level.  CPN_E_INVALID: N, H, W < 1, h1 / w1 outside 1 ... H / 1 ... W, c0 not 0 or a
+ *   positive multiple of 32, c1 or cout not positive multiples of 32, k not in {1, 3, 5, 7}, slab_rows < 0, x0 null with c0 > 0 or
+ *   the reverse, a null or unaligned pointer, an unknown dtype code.  CPN_E_UNSUPPORTED: more than 2^31 - 1 pixels or weights, more
+ *   than 65535 tiles of 64 x 64 channels, a chain longer than 2^31 - 1.  CPN_E_WORKSPACE: a workspace smaller than
+ *   cpn_cat_conv_wgrad_workspace_bytes = slabs * ((c0 + c1) * cout * k * k + cout) * 4.  Every call validates before it reads a
+ *   pointer.
+ *
+ * Saved for backward by cat_conv2d: x0 and x1 (bf16, x1 at its own low resolution) and w.  Known limits: T is written and read
+ * once (no footprint sum in the dgrad epilogue, no 4 x 4 stride-2 adjoint for the exact x2); the forward is not decomposed into
+ * sub-pixel phases; cpn_nearest_sum walks a footprint serially in one lane, so a tiny top under a large lateral (h = w = 1 at the
+ * extreme) leaves a handful of lanes reading the whole image: correct at any ratio, fast at the small ratios of a decoder.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_conv2d_sized(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const void *src1, int32_t c1_stride,
+                     const void *res, int32_t res_stride, void *dst, int32_t dst_stride, int32_t N, int32_t Hin, int32_t Win,
+                     const int32_t stored[6], const void *weights, const float *bias, void *stream);
+int64_t cpn_cat_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t h1, int32_t w1,
+                                           int32_t cout, int32_t k, int32_t slab_rows);
+int cpn_cat_conv_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t c0, int32_t c1, int32_t h1, int32_t w1, int32_t cout, int32_t k,
+                            int32_t slab_rows, int32_t info[5]);
+int cpn_cat_conv_wgrad(const void *x0, const void *x1, const void *dy, int32_t N, int32_t H, int32_t W, int32_t c0, int32_t c1,
+                       int32_t h1, int32_t w1, int32_t cout, int32_t k, int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype,
+                       void *db, int32_t db_dtype, void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, void *dst, int32_t h, int32_t w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
