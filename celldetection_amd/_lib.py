@@ -283,6 +283,16 @@ _SIGNATURES = [
                                           c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
                                           c_void_p]),
     ('cpn_nearest_sum', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    ('cpn_stem_train_pack', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_stem_train_forward', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_stem_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    ('cpn_stem_wgrad_workspace_bytes', c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    ('cpn_stem_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                      c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    ('cpn_maxpool2d_indexed', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                             c_void_p, c_void_p]),
+    ('cpn_maxpool2d_backward', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -17,7 +17,7 @@ Supported: ``groups = 1``, ``stride = 1``, ``dilation = 1``, a square odd ``k`` 
 ``Cin`` and ``Cout`` multiples of 32, a 4-D input on the GPU.  Everything else raises ``NotImplementedError`` naming the argument;
 there is no CPU fallback.  ``convert_conv2d_`` leaves every other conv and says why: the grouped 3x3 convs of the encoder are the
 business of ``grouped_conv2d``, the final 1x1 convs of the heads (1 / 2 / 20 output channels) of ``dropout_conv1x1``, both below.
-Known limit: the stem and the max-pool stay stock torch operations (the decoder's nearest resize with concat: ``cat_conv2d`` below).
+The stem (a 7x7 stride-2 conv from at most 4 channels) is ``stem_conv2d``'s, at the end of this module.
 
 Arithmetic: activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32, the forward output
 and the input gradient are stored as bf16, the weight and bias gradients are fp32 sums rounded once to the parameter's dtype.  ``x``
@@ -54,7 +54,18 @@ the resize instead of after it, and ``convert_unet_decoder_`` (the part after th
 convolution" section of include/cpn_hip.h).  After it a decoder level runs conv -> norm -> ReLU -> conv -> norm -> ReLU on
 ``(lateral, top)`` without a stock op.  Known limits: the top's gradient at the lateral's size is written once before it is summed
 (no footprint sum in the dgrad epilogue, no 4x4 stride-2 adjoint for the exact x2); the forward is not decomposed into sub-pixel
-phases; the stem, the max-pool and the bilinear resize behind the heads stay stock; ``cda.models.*`` stay inference-only.
+phases.
+
+The stem and the max-pool in front of ``layer1`` run here as well: ``stem_conv2d`` (one ``torch.autograd.Function``: the 7x7 stride-2
+conv from at most 4 channels on the inference stem's padded 4-channel layout, forward without ReLU, an MFMA weight gradient, no
+input gradient: the image needs none), the ``nn.Conv2d`` drop-in ``StemConv2d``, ``convert_stem_conv2d_``; ``max_pool2d`` for
+(3, 2, 1) and (2, 2, 0) (one ``uint8`` tap index per output element saved, the gradient a gather in a fixed order), the drop-in
+``MaxPool2d`` and ``convert_maxpool2d_`` (last part of this module; the rule is the "Trainable stem and max-pool" section of
+include/cpn_hip.h).  After ``convert_conv2d_``, ``convert_batchnorm2d_``, ``convert_grouped_conv2d_``, ``convert_bottleneck_`` and
+these two, in any order, an encoder runs without a stock operation.  Known limits: batch-norm statistics are not folded into the
+stem's epilogue; the pool is not fused into the norm's apply; the sum of the pool's gradient and a lateral's stays autograd's add;
+7x7 / stride 2 only (not the 3x3 first conv of the ``U22`` encoders); the bilinear resize behind the heads stays stock;
+``cda.models.*`` stay inference-only.
 """
 import ctypes
 
@@ -70,7 +81,9 @@ __all__ = ['conv2d', 'Conv2d', 'convert_conv2d_', 'is_supported', 'pack_weight',
            'grouped_pack_weight', 'grouped_dilate',
            'conv2d_fork', 'strided_conv1x1', 'StridedConv1x1', 'subsample2d', 'Bottleneck', 'convert_bottleneck_',
            'cat_conv2d', 'CatConv2d', 'cat_conv2d_weight_grad', 'cat_weight_grad_info', 'nearest_resize_backward', 'UNetDecoder',
-           'convert_unet_decoder_']
+           'convert_unet_decoder_',
+           'stem_conv2d', 'StemConv2d', 'convert_stem_conv2d_', 'stem_pack_weight', 'stem_weight_grad', 'stem_weight_grad_info',
+           'max_pool2d', 'MaxPool2d', 'convert_maxpool2d_']
 
 KERNEL_SIZES = (1, 3, 5, 7)
 _DTYPES = {torch.float32: _lib.CONV_TRAIN_F32, torch.bfloat16: _lib.CONV_TRAIN_BF16}
@@ -356,12 +369,12 @@ def convert_conv2d_(module):
     (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).  ``module`` itself is not replaced
     when it is a conv: it is reported as left."""
     replaced, left = [], {}
-    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, StridedConv1x1, CatConv2d)):
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, (Conv2d, StridedConv1x1, CatConv2d, StemConv2d)):
         left[''] = _why_not(module) or 'the root module cannot be replaced in place: convert its parent'
     for name, parent in list(module.named_modules()):
         for child_name, child in list(parent.named_children()):
             full = f'{name}.{child_name}' if name else child_name
-            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d)) or \
+            if isinstance(child, (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d, StemConv2d)) or \
                     not isinstance(child, torch.nn.modules.conv._ConvNd):
                 continue
             why = _why_not(child) if isinstance(child, torch.nn.Conv2d) else f'{type(child).__name__}: 2-D convs only'
@@ -2021,5 +2034,370 @@ def convert_unet_decoder_(module, decoder_types=()):
                 left[full] = why
                 continue
             setattr(parent, child_name, _decoder_from_torch(child))
+            replaced.append(full)
+    return replaced, left
+
+
+# ---- the stem of a ResNet encoder and the max-pool ("Trainable stem and max-pool" of include/cpn_hip.h, csrc/stem_train.hip,
+# csrc/pool_adjoint.h)
+#
+# The first two modules a step runs: ``Conv2d(in_channels <= 4, 64, 7, stride=2, padding=3)`` and ``MaxPool2d(3, 2, 1)`` (the
+# reference's ``models/resnet.py:274-284``), and the ``MaxPool2d(2, 2)`` of the U-Net encoders.  ``stem_conv2d`` converts the image
+# to the padded 4-channel bf16 layout of the inference stem (csrc/stem.hip), in which the 7 taps of a filter row are contiguous,
+# and saves that tensor alone; the weight gradient is seven MFMA products per slab, one per filter row, with the flat output pixel as
+# the reduction index.  The image gets no gradient.  ``max_pool2d`` stores one ``uint8`` tap index per output element and saves
+# nothing else; its backward is a gather in a fixed order (no atomics, no scatter).
+
+STEM_OUT_CHANNELS = (32, 64)
+STEM_MAX_IN_CHANNELS = 4
+POOL_GEOMETRIES = ((3, 2, 1), (2, 2, 0))
+
+
+def _stem_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels, transposed=False):
+    """The first argument the trainable stem does not run, as a sentence, or None."""
+    if transposed:
+        return 'transposed convs are not run'
+    if _pair(kernel_size) != (7, 7):
+        return f'kernel_size {kernel_size}: 7x7 only'
+    if _pair(stride) != (2, 2):
+        return f'stride {stride}: stride 2 only'
+    if isinstance(padding, str) or _pair(padding) != (3, 3):
+        return f'padding {padding}: 3 zeros only'
+    if _pair(dilation) != (1, 1):
+        return f'dilation {dilation}: dilation 1 only'
+    if groups != 1:
+        return f'groups {groups}: dense convs only'
+    if padding_mode != 'zeros':
+        return f"padding_mode '{padding_mode}': zeros only"
+    if not 1 <= in_channels <= STEM_MAX_IN_CHANNELS:
+        return f'in_channels {in_channels}: 1 ... {STEM_MAX_IN_CHANNELS} only'
+    if out_channels not in STEM_OUT_CHANNELS:
+        return f'out_channels {out_channels}: {STEM_OUT_CHANNELS} only'
+    return None
+
+
+def _check_stem_weight(weight):
+    if weight.dim() != 4:
+        raise NotImplementedError(f'weight of {weight.dim()} dimensions: the trainable stem needs [Cout, C, 7, 7]')
+    if tuple(weight.shape[2:]) != (7, 7):
+        raise NotImplementedError(f'kernel_size {tuple(weight.shape[2:])}: the trainable stem runs 7x7 kernels only')
+    if weight.dtype not in _DTYPES:
+        raise NotImplementedError(f'weight dtype {weight.dtype}: the trainable stem takes float32 or bfloat16 parameters')
+    if not 1 <= int(weight.shape[1]) <= STEM_MAX_IN_CHANNELS:
+        raise NotImplementedError(f'in_channels {int(weight.shape[1])}: the trainable stem takes 1 ... {STEM_MAX_IN_CHANNELS}')
+    if int(weight.shape[0]) not in STEM_OUT_CHANNELS:
+        raise NotImplementedError(f'out_channels {int(weight.shape[0])}: the trainable stem writes {STEM_OUT_CHANNELS} only')
+
+
+def _check_stem_input(x):
+    if x.dim() != 4:
+        raise NotImplementedError(f'input of {x.dim()} dimensions: the trainable stem takes a 4-D [N, C, H, W] input')
+    if x.dtype not in _DTYPES:
+        raise NotImplementedError(f'input dtype {x.dtype}: the trainable stem takes float32 or bfloat16 images')
+    if not 1 <= int(x.shape[1]) <= STEM_MAX_IN_CHANNELS:
+        raise NotImplementedError(f'input of {int(x.shape[1])} channels: the trainable stem takes 1 ... {STEM_MAX_IN_CHANNELS}')
+    if min(int(v) for v in x.shape) < 1:
+        raise NotImplementedError(f'input of size {tuple(x.shape)}: the trainable stem needs at least one pixel')
+
+
+def stem_pack_weight(weight):
+    """weight [Cout, C, 7, 7] (float32 | bfloat16, on the GPU) -> the bf16 records [7][Cout][32] the stem loop reads, packed on the
+    device: filter row, output channel, (kx 0..7, c 0..3) with zeros at kx = 7 and c >= C."""
+    _check_stem_weight(weight)
+    _need_cuda(weight)
+    w = weight.detach().contiguous()
+    cout, c = int(w.shape[0]), int(w.shape[1])
+    packed = torch.empty((7, cout, 32), dtype=torch.bfloat16, device=w.device)
+    _lib.check(_lib.load().cpn_stem_train_pack(_lib.ptr(w), _DTYPES[w.dtype], cout, c, _lib.ptr(packed), _lib.stream_ptr()),
+               'stem_train_pack')
+    return packed
+
+
+def _stem_pad(x):
+    """x [N, C <= 4, H, W] -> the padded input bf16 [N, H + 6, W + 8, 4] (zero border, zeros in the channels >= C)."""
+    n, c, h, w = (int(v) for v in x.shape)
+    src = x.detach().float().contiguous()  # (bf16 -> fp32 is exact; the kernel rounds fp32 to bf16, to nearest even)
+    xp = torch.empty((n, h + 6, w + 8, 4), dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().cpn_convert_input_stem(_lib.ptr(src), 0, _lib.ptr(xp), n, c, h, w, None, _lib.stream_ptr()),
+               'convert_input_stem')
+    return xp
+
+
+def _stem_forward(xp, size, packed, bias):
+    n, h, w = size
+    cout = int(packed.shape[1])
+    out = torch.empty((n, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.bfloat16, device=xp.device,
+                      memory_format=torch.channels_last)
+    _lib.check(_lib.load().cpn_stem_train_forward(_lib.ptr(xp), _lib.ptr(packed), _lib.ptr(bias), n, h, w, cout, _lib.ptr(out),
+                                                  _lib.stream_ptr()), 'stem_train_forward')
+    return out
+
+
+def stem_weight_grad_info(n, h, w, cout, slab_rows=0):
+    """What ``stem_weight_grad`` would run on an ``h x w`` image -> dict(slabs, slab_rows (output rows per slab), steps (MFMA steps
+    per slab), reduce_chain, bias_chain).  Host arithmetic only: needs no GPU.  Raises like the launch for a call it rejects."""
+    info = (ctypes.c_int32 * 5)()
+    _lib.check(_lib.load().cpn_stem_wgrad_info(n, h, w, cout, slab_rows, info), 'stem_wgrad_info')
+    return dict(zip(('slabs', 'slab_rows', 'steps', 'reduce_chain', 'bias_chain'), (int(v) for v in info)))
+
+
+def _stem_wgrad(xp, size, c, gs, slab_rows, weight, bias, dtype, bias_dtype):
+    """xp: the padded input; gs: bf16 NHWC memory, 16-byte aligned -> (dW | None, db | None)."""
+    n, h, w = size
+    cout = int(gs.shape[1])
+    dw = torch.zeros((cout, c, 7, 7), dtype=dtype, device=xp.device) if weight else None
+    db = torch.zeros((cout,), dtype=bias_dtype, device=xp.device) if bias else None
+    if not (weight or bias):
+        return dw, db
+    lib = _lib.load()
+    nbytes = int(lib.cpn_stem_wgrad_workspace_bytes(n, h, w, cout, slab_rows))
+    if nbytes <= 0:
+        _lib.check(lib.cpn_stem_wgrad_info(n, h, w, cout, slab_rows, (ctypes.c_int32 * 5)()), 'stem_wgrad')
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=xp.device)
+    _lib.check(lib.cpn_stem_wgrad(_lib.ptr(xp), _lib.ptr(gs), n, h, w, c, cout, slab_rows, _lib.ptr(dw), _DTYPES[dtype], _lib.ptr(db),
+                                  _DTYPES[bias_dtype], _lib.ptr(ws), nbytes, _lib.stream_ptr()), 'stem_wgrad')
+    return dw, db
+
+
+def stem_weight_grad(x, grad_output, slab_rows=0, weight=True, bias=True, dtype=torch.float32, bias_dtype=None):
+    """(x [N, C <= 4, H, W], grad_output [N, Cout, Hout, Wout]) -> (dW [Cout, C, 7, 7] | None, db [Cout] | None): the gradients
+    ``stem_conv2d`` returns for its weight and bias, as fp32 sums over the bf16-rounded operands rounded once to ``dtype`` /
+    ``bias_dtype``.  ``slab_rows``: output rows per slab of the reduction (0: chosen by the library)."""
+    _check_stem_input(x)
+    n, c, h, w = (int(v) for v in x.shape)
+    cout = int(grad_output.shape[1])
+    if cout not in STEM_OUT_CHANNELS:
+        raise NotImplementedError(f'out_channels {cout}: the trainable stem writes {STEM_OUT_CHANNELS} only')
+    bias_dtype = dtype if bias_dtype is None else bias_dtype
+    if dtype not in _DTYPES or bias_dtype not in _DTYPES:
+        raise NotImplementedError(f'dtype {dtype} / {bias_dtype}: gradients are float32 or bfloat16')
+    want = (n, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    assert tuple(grad_output.shape) == want, (tuple(grad_output.shape), want)
+    _need_cuda(x, grad_output)
+    return _stem_wgrad(_stem_pad(x), (n, h, w), c, _nhwc(grad_output, torch.bfloat16), slab_rows, weight, bias, dtype, bias_dtype)
+
+
+class _StemConv2dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        n, c, h, w = (int(v) for v in x.shape)
+        xp = _stem_pad(x)
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        out = _stem_forward(xp, (n, h, w), stem_pack_weight(weight), b32)
+        ctx.save_for_backward(xp)  # the padded bf16 input alone: neither x nor the weight is needed again
+        ctx.size, ctx.c = (n, h, w), c
+        ctx.weight_dtype = weight.dtype
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        xp, = ctx.saved_tensors
+        _, need_w, need_b = ctx.needs_input_grad
+        need_b = need_b and ctx.bias_dtype is not None
+        dw = db = None
+        if need_w or need_b:
+            dw, db = _stem_wgrad(xp, ctx.size, ctx.c, _nhwc(grad_output, torch.bfloat16), 0, need_w, need_b, ctx.weight_dtype,
+                                 ctx.bias_dtype or ctx.weight_dtype)
+        return None, dw, db
+
+
+def stem_conv2d(x, weight, bias=None):
+    """``torch.nn.functional.conv2d(x, weight, bias, stride=2, padding=3)`` for a 7x7 ``weight [Cout in {32, 64}, C <= 4, 7, 7]`` ->
+    bf16 [N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1] in ``torch.channels_last``, with gradients for ``weight`` and ``bias`` as
+    autograd asks for them.  The image gets no gradient: ``x.requires_grad`` raises ``NotImplementedError``."""
+    _check_stem_input(x)
+    _check_stem_weight(weight)
+    if int(x.shape[1]) != int(weight.shape[1]):
+        raise ValueError(f'input has {int(x.shape[1])} channels, weight expects {int(weight.shape[1])}')
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] != weight.shape[0] or bias.dtype not in _DTYPES):
+        raise NotImplementedError(f'bias {tuple(bias.shape)} {bias.dtype}: the trainable stem takes a float32 or bfloat16 [Cout] bias')
+    if x.requires_grad:
+        raise NotImplementedError('x requires a gradient: the trainable stem has no input gradient (the image needs none; detach x)')
+    _need_cuda(x, weight, bias)
+    return _StemConv2dFunction.apply(x, weight, bias)
+
+
+class StemConv2d(torch.nn.Conv2d):
+    """``torch.nn.Conv2d`` with torch's constructor arguments and parameter names (``weight``, ``bias``: ``state_dict``s
+    interchange) whose forward is ``stem_conv2d``.  ``kernel_size``, ``stride`` and ``padding`` default to 7, 2 and 3; an argument
+    outside the supported family raises ``NotImplementedError`` naming it."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=7, stride=2, padding=3, dilation=1, groups=1, bias=True,
+                 padding_mode='zeros', device=None, dtype=None):
+        why = _stem_unsupported(kernel_size, stride, padding, dilation, groups, padding_mode, in_channels, out_channels)
+        if why is not None:
+            raise NotImplementedError(why)
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device, dtype)
+
+    def forward(self, x):
+        return stem_conv2d(x, self.weight, self.bias)
+
+
+def _stem_why_not(conv):
+    if type(conv) is not torch.nn.Conv2d:
+        return f'a subclass of torch.nn.Conv2d ({type(conv).__name__}): its forward may differ'
+    if conv.weight.dtype not in _DTYPES:
+        return f'weight dtype {conv.weight.dtype}: float32 or bfloat16 only'
+    return _stem_unsupported(conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.padding_mode,
+                             conv.in_channels, conv.out_channels, conv.transposed)
+
+
+def _stem_from_torch(conv):
+    new = StemConv2d.__new__(StemConv2d)
+    new.__dict__.update(conv.__dict__)  # the same Parameter objects, hooks, training flag and constructor attributes
+    new._parameters = dict(conv._parameters)  # (the registry itself is the new module's own)
+    return new
+
+
+def _our_convs():
+    return Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d, StemConv2d
+
+
+def _is_stem_business(conv):
+    """A conv from at most 4 channels, or a 7x7 conv of stride 2: what a reader would take for a stem."""
+    return conv.in_channels <= STEM_MAX_IN_CHANNELS or (_pair(conv.kernel_size) == (7, 7) and _pair(conv.stride) == (2, 2))
+
+
+def convert_stem_conv2d_(module):
+    """Replaces every eligible plain ``torch.nn.Conv2d`` below ``module`` -- ``in_channels <= 4``, ``out_channels`` 32 or 64, 7x7,
+    stride 2, padding 3 with zeros, dilation 1, groups 1 -- in place by a ``StemConv2d`` that shares its ``Parameter`` objects
+    (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).  ``left`` names every other conv
+    from at most 4 channels and every other 7x7 conv of stride 2 with the reason; the remaining convs are not its business.
+    ``module`` itself is not replaced when it is such a conv: it is reported as left.  A conv object that sits in several slots is
+    replaced by one object in all of them.  Works before or after the other converts."""
+    replaced, left = [], {}
+    ours = _our_convs()
+    if isinstance(module, torch.nn.Conv2d) and not isinstance(module, ours) and _is_stem_business(module):
+        left[''] = _stem_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
+    swapped = {}  # id of a replaced conv -> its replacement: a conv in two slots stays one object
+    for name, parent in list(module.named_modules()):
+        slots = [(n, c) for n, c in parent._modules.items() if c is not None]  # (named_children() drops repeated objects)
+        for child_name, child in slots:
+            full = f'{name}.{child_name}' if name else child_name
+            if not isinstance(child, torch.nn.Conv2d) or isinstance(child, ours) or not _is_stem_business(child):
+                continue
+            why = _stem_why_not(child)
+            if why is not None:
+                left[full] = why
+                continue
+            if id(child) not in swapped:
+                swapped[id(child)] = _stem_from_torch(child)
+            setattr(parent, child_name, swapped[id(child)])
+            replaced.append(full)
+    return replaced, left
+
+
+def _pool_unsupported(kernel_size, stride, padding, dilation=1, ceil_mode=False, return_indices=False):
+    """The first argument the trainable max-pool does not run, as a sentence, or None."""
+    if _pair(dilation) != (1, 1):
+        return f'dilation {dilation}: dilation 1 only'
+    if ceil_mode:
+        return 'ceil_mode True: floor mode only'
+    if return_indices:
+        return 'return_indices True: the tap index stays inside the function'
+    k, s, p = _pair(kernel_size), _pair(kernel_size if stride is None else stride), _pair(padding)
+    if k[0] != k[1] or s[0] != s[1] or p[0] != p[1] or (k[0], s[0], p[0]) not in POOL_GEOMETRIES:
+        return f'kernel_size {kernel_size}, stride {stride}, padding {padding}: (kernel_size, stride, padding) in {POOL_GEOMETRIES} only'
+    return None
+
+
+class _MaxPool2dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k, s, pad):
+        n, c, h, w = (int(v) for v in x.shape)
+        ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
+        xs = _nhwc(x)
+        y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        index = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device)
+        _lib.check(_lib.load().cpn_maxpool2d_indexed(_lib.ptr(xs), _DTYPES[x.dtype], n, h, w, c, k, s, pad, _lib.ptr(y), _lib.ptr(index),
+                                                     _lib.stream_ptr()), 'maxpool2d_indexed')
+        ctx.save_for_backward(index)  # one byte per output element; neither x nor y
+        ctx.geometry, ctx.size, ctx.dtype = (k, s, pad), (n, c, h, w), x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        index, = ctx.saved_tensors
+        n, c, h, w = ctx.size
+        k, s, pad = ctx.geometry
+        gs = _nhwc(grad_output, ctx.dtype)
+        dx = torch.empty((n, c, h, w), dtype=ctx.dtype, device=gs.device, memory_format=torch.channels_last)
+        _lib.check(_lib.load().cpn_maxpool2d_backward(_lib.ptr(gs), _lib.ptr(index), _DTYPES[ctx.dtype], n, h, w, c, k, s, pad,
+                                                      _lib.ptr(dx), _lib.stream_ptr()), 'maxpool2d_backward')
+        return dx, None, None, None
+
+
+def max_pool2d(x, kernel_size, stride=None, padding=0, dilation=1, ceil_mode=False, return_indices=False):
+    """``torch.nn.functional.max_pool2d`` for ``(kernel_size, stride, padding)`` = (3, 2, 1) or (2, 2, 0) on a 4-D float32 or
+    bfloat16 input with ``C`` a positive multiple of 8 -> the output in ``x``'s dtype and ``torch.channels_last``, with torch's tie
+    rule (the first maximum of a window in raster order takes the gradient).  Saves one ``uint8`` per output element.  Inputs are
+    finite: NaN is outside the contract."""
+    why = _pool_unsupported(kernel_size, stride, padding, dilation, ceil_mode, return_indices)
+    if why is not None:
+        raise NotImplementedError(why)
+    if x.dim() != 4:
+        raise NotImplementedError(f'input of {x.dim()} dimensions: the trainable max-pool takes a 4-D [N, C, H, W] input')
+    if x.dtype not in _DTYPES:
+        raise NotImplementedError(f'input dtype {x.dtype}: the trainable max-pool takes float32 or bfloat16 activations')
+    n, c, h, w = (int(v) for v in x.shape)
+    if c < 8 or c % 8:
+        raise NotImplementedError(f'input of {c} channels (C % 8 != 0): the trainable max-pool needs a positive multiple of 8')
+    k, pad = _pair(kernel_size)[0], _pair(padding)[0]
+    s = k if stride is None else _pair(stride)[0]
+    if n < 1 or h + 2 * pad < k or w + 2 * pad < k:
+        raise ValueError(f'input of size {tuple(x.shape)}: the output of a {k}x{k} pool would be empty')
+    _need_cuda(x)
+    return _MaxPool2dFunction.apply(x, k, s, pad)
+
+
+class MaxPool2d(torch.nn.MaxPool2d):
+    """``torch.nn.MaxPool2d`` with torch's constructor arguments whose forward is ``max_pool2d``; an argument outside the supported
+    family raises ``NotImplementedError`` naming it."""
+
+    def __init__(self, kernel_size, stride=None, padding=0, dilation=1, return_indices=False, ceil_mode=False):
+        why = _pool_unsupported(kernel_size, stride, padding, dilation, ceil_mode, return_indices)
+        if why is not None:
+            raise NotImplementedError(why)
+        super().__init__(kernel_size, stride, padding, dilation, return_indices, ceil_mode)
+
+    def forward(self, x):
+        return max_pool2d(x, self.kernel_size, self.stride, self.padding)
+
+
+def _pool_why_not(pool):
+    if type(pool) is not torch.nn.MaxPool2d:
+        return f'a subclass of torch.nn.MaxPool2d ({type(pool).__name__}): its forward may differ'
+    return _pool_unsupported(pool.kernel_size, pool.stride, pool.padding, pool.dilation, pool.ceil_mode, pool.return_indices)
+
+
+def _pool_from_torch(pool):
+    new = MaxPool2d.__new__(MaxPool2d)
+    new.__dict__.update(pool.__dict__)  # hooks, training flag and constructor attributes
+    return new
+
+
+def convert_maxpool2d_(module):
+    """Replaces every plain ``torch.nn.MaxPool2d`` of the two geometries below ``module`` in place by a ``MaxPool2d`` -> (names
+    replaced, {name left: reason}).  Every other max-pool is left with a reason naming the argument (``C % 8`` shows at run time
+    only: there the forward raises).  ``module`` itself is not replaced when it is a pool: it is reported as left.  A pool object
+    that sits in several slots is replaced by one object in all of them.  Works before or after the other converts."""
+    replaced, left = [], {}
+    if isinstance(module, torch.nn.MaxPool2d) and not isinstance(module, MaxPool2d):
+        left[''] = _pool_why_not(module) or 'the root module cannot be replaced in place: convert its parent'
+    swapped = {}
+    for name, parent in list(module.named_modules()):
+        slots = [(n, c) for n, c in parent._modules.items() if c is not None]  # (named_children() drops repeated objects)
+        for child_name, child in slots:
+            full = f'{name}.{child_name}' if name else child_name
+            if not isinstance(child, torch.nn.MaxPool2d) or isinstance(child, MaxPool2d):
+                continue
+            why = _pool_why_not(child)
+            if why is not None:
+                left[full] = why
+                continue
+            if id(child) not in swapped:
+                swapped[id(child)] = _pool_from_torch(child)
+            setattr(parent, child_name, swapped[id(child)])
             replaced.append(full)
     return replaced, left

@@ -1307,6 +1307,78 @@ int cpn_cat_conv_wgrad(const void *x0, const void *x1, const void *dy, int32_t N
                        void *db, int32_t db_dtype, void *workspace, int64_t workspace_bytes, void *stream);
 int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, void *dst, int32_t h, int32_t w, void *stream);
 
+/* ---- Trainable stem and max-pool ----------------------------------------------------------------------------
+ * What celldetection_amd.nn.stem_conv2d and nn.max_pool2d run: the first two modules of a ResNet / ResNeXt encoder,
+ * Conv2d(C <= 4 -> 32 | 64, 7x7, stride 2, padding 3) and MaxPool2d(3, 2, 1), and the MaxPool2d(2, 2) of the U-Net encoders
+ * (csrc/stem_train.hip, csrc/pool_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the
+ * contract.
+ *
+ * The stem's input is the padded 4-channel tensor Xp, bf16 [N][H + 6][W + 8][4] with a zero border (3 rows / columns in front) and
+ * zeros in the channels c >= C, as cpn_convert_input_stem writes it (range_flag = NULL: a training input need not lie in [0, 1]).
+ * Hout = (H - 1) / 2 + 1, Wout = (W - 1) / 2 + 1.  The 32 values (kx 0..7, c 0..3) that output pixel (oy, ox) meets in filter row
+ * ky are the 64 contiguous bytes at Xp[n][2 oy + ky][2 ox]; every such read lies inside Xp, the last row of the last image
+ * included.  Arithmetic: operands are rounded to bf16 (round to nearest even), sums are fp32, every stored value is rounded once.
+ *
+ *   cpn_stem_train_pack: weight [cout][cin][7][7] (weight_dtype 0 = fp32 | 1 = bf16) -> packed [7][cout][32] bf16: filter row,
+ *   output channel, (kx 0..7, c 0..3), zeros at kx = 7 and c >= cin -- the layout of CPN_OP_STEM7.  Round to nearest even, fp32
+ *   subnormals included; bf16 weights are copied.  Runs on the device every step.  cout 32 | 64, 1 <= cin <= 4 (CPN_E_INVALID).
+ *
+ *   cpn_stem_train_forward: y[n][oy][ox][co] = sum over (ky, kx, c) of Xp[n][2 oy + ky][2 ox + kx][c] * packed[ky][co][kx][c]
+ *   (+ bias[co], fp32, may be NULL), bf16 NHWC [N][Hout][Wout][cout], no activation.  The loop of the inference stem
+ *   (csrc/stem.hip): 14 v_mfma_f32_32x32x16_bf16 steps per output in one fp32 accumulator, + 2 for the MFMA-internal sum, + the
+ *   bias add, one rounding to bf16.
+ *
+ *   cpn_stem_wgrad: dw[co][c][ky][kx] = sum over (n, oy, ox) of dY[n][oy][ox][co] * Xp[n][2 oy + ky][2 ox + kx][c] for kx < 7 and
+ *   c < cin; dY bf16 NHWC [N][Hout][Wout][cout].  The reduction index is the flat output pixel p = (n Hout + oy) Wout + ox.  Slabs
+ *   of slab_rows output rows of the N * Hout rows (0 = auto: at most 256 slabs of equal size; csrc/wgrad_slabs.h); inside a slab
+ *   the pixels in ascending order, 16 per MFMA step, in ONE fp32 accumulator per element (no cross-wave sum: one wave owns a filter
+ *   row of a slab from its first pixel to its last); pixels behind a slab's end are zeros in both operands.  The slabs' partial
+ *   sums, workspace [slab][7][cout][32] fp32, are added in ascending slab order (+ one add per slab) and rounded once to dw_dtype;
+ *   the columns kx = 7 and c >= cin are never read, so they never reach dw.  db[co] = the sum of dY, by the bias kernels of
+ *   cpn_conv_wgrad: 8 interleaved chains per slab added in order, then the slabs in ascending slab order.  No floating-point
+ *   atomics: bit-identical from run to run.  There is no input gradient.
+ *   cpn_stem_wgrad_info: info[5] = {slabs, slab_rows, MFMA steps of the largest slab, reduce chain, bias chain}; the chain of one
+ *   dw element is info[2] + 2 + info[3].  cpn_stem_wgrad_workspace_bytes = slabs * (7 * cout * 32 + cout) * 4.  Both answer
+ *   without a GPU.  H and W are the IMAGE's size.
+ *   CPN_E_INVALID: N, H, W < 1, cout not 32 | 64, cin outside 1 ... 4, slab_rows < 0, a null or unaligned (16 bytes) pointer, dw
+ *   and db both null, an unknown dtype code.  CPN_E_UNSUPPORTED: more than 2^31 - 1 pixels in Xp.  CPN_E_WORKSPACE: a workspace
+ *   smaller than cpn_stem_wgrad_workspace_bytes.  Every call validates before it reads a pointer.
+ *
+ * The pool.  (k, stride, pad) = (3, 2, 1) or (2, 2, 0); x [N][H][W][C] NHWC, dtype 0 = fp32 | 1 = bf16, C a positive multiple of
+ * 8, 16 bytes per lane; Hout = (H + 2 pad - k) / stride + 1 >= 1, Wout likewise.  Inputs are finite: NaN is outside the contract.
+ *
+ *   cpn_maxpool2d_indexed: y [N][Hout][Wout][C] in x's dtype and index, one uint8 per element of y.  Tie rule (torch's): the
+ *   window's positions (oy stride - pad + ty, ox stride - pad + tx) are scanned in raster order of (ty, tx); positions outside the
+ *   image do not exist (the window is cut at the border, not clamped); a position takes the window over only when its value is
+ *   strictly greater, so the first maximum wins (-0 and +0 are equal: the first of them).  index = ty * k + tx of the winner.  y is
+ *   the winner's value, bit for bit what cpn_maxpool2d gives.
+ *
+ *   cpn_maxpool2d_backward: dx [N][H][W][C] from dY and index.  A lane owns 16 bytes of one input pixel (iy, ix) and visits the at
+ *   most 2 x 2 windows that cover it, in raster order of (oy, ox); where index[oy][ox] names the tap this pixel is in that window it
+ *   adds dY[oy][ox] in fp32 (at most 4 terms: 3 adds), and rounds once to the tensor's dtype.  A pixel no window names, or no
+ *   window covers (the odd last row or column at (2, 2, 0)), gets an exact 0.  No atomics, no scatter: bit-identical from run to
+ *   run.  Which windows cover a pixel and which tap it is there: csrc/pool_adjoint.h (integer only, also compiled for the host).
+ *   CPN_E_INVALID: N, H, W < 1, C not a positive multiple of 8, an unknown dtype code, another geometry, an axis shorter than a
+ *   window, a null or unaligned (16 bytes) pointer.  CPN_E_UNSUPPORTED: more than 2^31 - 1 pixels or workgroups.
+ *
+ * Saved for backward: by stem_conv2d Xp alone (4 channels for the image's 3: a third more than the image in bf16, plus the border), by
+ * max_pool2d the uint8 index alone.  Known limits: no input gradient of the stem; batch-norm statistics are not folded into the
+ * stem's epilogue; the pool is not fused into the norm's apply; the weight gradient stages every pixel's 64 bytes of Xp on their
+ * own (the overlap of neighbouring pixels is left to the caches); 7x7 / stride 2 only.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_stem_train_pack(const void *weight, int32_t weight_dtype, int32_t cout, int32_t cin, void *packed, void *stream);
+int cpn_stem_train_forward(const void *xp, const void *packed, const float *bias, int32_t N, int32_t H, int32_t W, int32_t cout,
+                           void *y, void *stream);
+int cpn_stem_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cout, int32_t slab_rows, int32_t info[5]);
+int64_t cpn_stem_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t cout, int32_t slab_rows);
+int cpn_stem_wgrad(const void *xp, const void *dy, int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                   int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db, int32_t db_dtype, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+int cpn_maxpool2d_indexed(const void *x, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride,
+                          int32_t pad, void *y, void *index, void *stream);
+int cpn_maxpool2d_backward(const void *dy, const void *index, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k,
+                           int32_t stride, int32_t pad, void *dx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
