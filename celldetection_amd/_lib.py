@@ -283,6 +283,14 @@ _SIGNATURES = [
                                           c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
                                           c_void_p]),
     ('cpn_nearest_sum', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    ('cpn_resized_conv_wgrad_workspace_bytes', c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                         c_int32]),
+    ('cpn_resized_conv_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                   POINTER(c_int32)]),
+    ('cpn_resized_conv_wgrad', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    ('cpn_bilinear_sum', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    ('cpn_bilinear_sum_f32', ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     ('cpn_stem_train_pack', ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     ('cpn_stem_train_forward', ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     ('cpn_stem_wgrad_info', ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),

@@ -61,6 +61,10 @@ SOURCES = {
     # trainable concat conv of the decoder: the weight gradient over the virtual concat of the lateral and the nearest-resized top,
     # and the adjoint of the resize (index arithmetic: csrc/nearest_adjoint.h)
     'cat_conv_train.hip': [],
+    # trainable bilinear resize of the refinement head: the adjoint of the resize as a gather (activations and fp32 planes) and the
+    # weight gradient of a conv over the virtual resized tensor; the blend and the sums are defined by their order of operations
+    # (index arithmetic: csrc/bilinear_adjoint.h): no FMA contraction
+    'bilinear_train.hip': ['-ffp-contract=off'],
     # trainable ResNet stem (7x7 stride-2 conv on the padded 4-channel input: pack, forward, weight gradient) and max-pool with its
     # tap index and gather gradient (index arithmetic: csrc/pool_adjoint.h)
     'stem_train.hip': [],
@@ -72,7 +76,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'grouped_conv.h', 'nearest_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -1379,6 +1379,80 @@ int cpn_maxpool2d_indexed(const void *x, int32_t dtype, int32_t N, int32_t H, in
 int cpn_maxpool2d_backward(const void *dy, const void *index, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k,
                            int32_t stride, int32_t pad, void *dx, void *stream);
 
+/* ---- Trainable bilinear resize ------------------------------------------------------------------------------
+ * What celldetection_amd.nn.bilinear_resize and nn.resized_conv2d need besides cpn_resize_bilinear, cpn_resize_bilinear_f32,
+ * cpn_conv2d_sized and the "Trainable convolution" section to train the refinement head of a CPN: the resize of the refinement
+ * features to the input's size in front of the head's k x k conv, and the resize of the head maps (csrc/bilinear_train.hip,
+ * csrc/bilinear_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * The map.  B is F.interpolate(mode='bilinear', align_corners=False) from h x w to H x W, 1 <= h <= H, 1 <= w <= W.  Per axis,
+ * output index dst reads
+ *     f = fmaxf(scale * ((float) dst + 0.5f) - 0.5f, 0.f),  i0 = (int) f,  i1 = i0 + (i0 < in - 1),  lambda = f - (float) i0,
+ *     scale = (float) in / (float) out,
+ * as (1 - lambda) * src[i0] + lambda * src[i1]: the rule of bilinear_kernel, of the conv loader's halo_bilinear_store and of
+ * resize_f32_kernel, restated as ba_tap in csrc/bilinear_adjoint.h.  The text leaves open how often the coordinate is rounded, and
+ * the forward kernels differ in it: bilinear_kernel and the conv loader are compiled with contraction, which makes the product and
+ * the difference ONE fma (the fused form: one rounding); resize_f32_kernel rounds each (the split form).  The forms agree where the
+ * product is exact (the exact x2 among them) and differ by its rounding elsewhere (lambda by at most 2^-24 * in; where f falls on
+ * an integer, the tap pair).  ba_tap states both, and every backward uses the form of ITS forward: fused for activations and for
+ * the resized conv, split for the fp32 planes.  Everything after the coordinate is rounded to fp32 operation by operation (no
+ * contraction).  Equal sizes make an axis the identity (f = dst, lambda = 0).  With hy = 1 - ly and hx = 1 - lx,
+ *     B(x)[n][y][x] = hy * (hx * x[y0][x0] + lx * x[y0][x1]) + ly * (hx * x[y1][x0] + lx * x[y1][x1]).
+ * i0 is non-decreasing in dst, so the outputs that touch source index i, those with i0 in {i - 1, i}, are one contiguous range
+ * [ba_first(i - 1), ba_first(i + 1)), never empty; every output lies in two such ranges per axis, in one at the clamped last
+ * index.  ba_weight(dst, i) = (i == i0) * (1 - lambda) + (i == i1) * lambda: at the clamped last index both terms apply.
+ *
+ * The adjoint.  For T at H x W, B^T(T)[n][i][j][c] = the sum over the footprint of (i, j) -- rows [ba_first(i - 1), ba_first(i + 1))
+ * times columns likewise, in ascending row-major (y, x) order -- of c(y, x) * T[n][y][x][c] with the coefficient
+ * c = ba_weight(y, i) * ba_weight(x, j) formed first (one fp32 product), then one multiply and one add per term, no fma, all in
+ * fp32.  A gather: no floating-point atomics, no scatter, bit-identical from run to run.  At the exact x2 a footprint is
+ * 4 x 4 (5 wide at source index 1, which the clamp at 0 gives a third output of index 0).
+ *   cpn_bilinear_sum: bf16 NHWC T [N][H][W][C] -> bf16 [N][h][w][C], one rounding (RNE).  16 bytes (8 channels) per lane; C a
+ *   positive multiple of 8, N, H, W >= 1, 1 <= h <= H, 1 <= w <= W (CPN_E_INVALID otherwise), N * H * W <= 2^31 - 1
+ *   (CPN_E_UNSUPPORTED above), t and dst 16-byte aligned.
+ *   cpn_bilinear_sum_f32: fp32 planes T [P][H][W] -> fp32 [P][h][w], the fp32 sum stored as it is; one lane per source pixel of one
+ *   plane; the same checks with P in place of N, 4-byte alignment.  The backward of cpn_resize_bilinear_f32, whose taps are the same
+ *   (its blend adds the column pair first: (v00 * hx + v01 * lx) * hy + (v10 * hx + v11 * lx) * ly).
+ * Every call validates before it reads a pointer.
+ *
+ * The resized convolution.  y = conv(B(x), w) + b with x [N][h][w][cin] bf16 NHWC, w [cout][cin][k][k], k in {3, 5, 7}, stride 1,
+ * padding k / 2 with zeros, cin and cout positive multiples of 32.  B(x) is never written.
+ * Forward: cpn_conv2d_sized with up0 = 2 and stored = {h, w, ...} on the forward pack of w: the loader blends (MODE_BL of
+ * csrc/conv_igemm.hip; compiled with contraction, so its blend may differ from the stated one in the last fp32 bit before the
+ * rounding to bf16).
+ * Input gradient: T = the dgrad conv of dY at H x W (bf16, "Trainable convolution"), then dx = B^T(T) by cpn_bilinear_sum.
+ * Weight and bias gradients: dw[co][ci][ky][kx] = sum over pixels p of dY[p][co] * X[p + (ky - pad) * W + (kx - pad)][ci] with zeros
+ * outside the image, where X = bf16(B(x)): the blend above in fp32 on the bf16 x, rounded to bf16 (RNE) when it is staged.
+ * Partition, chains and rounding are those of cpn_conv_wgrad: slabs of slab_rows image rows of the N * H rows, 16 pixels per MFMA
+ * step in one fp32 accumulator per output, then the slabs' partial sums added in ascending slab order (+ one add per slab), rounded
+ * once to dw_dtype; db likewise from dY alone.  No floating-point atomics: bit-identical from run to run.  The four source pixels
+ * (negative outside the tensor) and the two lambdas of each staged row are computed once per 128-pixel chunk into an LDS table;
+ * every 16-byte item loads its four source items and blends.
+ *   cpn_resized_conv_wgrad_info / cpn_resized_conv_wgrad_workspace_bytes / cpn_resized_conv_wgrad: the argument order of
+ *   cpn_conv_wgrad_info / _workspace_bytes / cpn_conv_wgrad with (cin, h, w) in place of cin; H x W is the size of dY.  info[5] =
+ *   {slabs, slab_rows, MFMA steps of the largest slab, reduce chain, bias chain}; the chain of one dw element is info[2] + 2 +
+ *   info[3].  info and workspace_bytes answer without a GPU.  CPN_E_INVALID: N, H, W < 1, h / w outside 1 ... H / 1 ... W, cin or
+ *   cout not positive multiples of 32, k not in {3, 5, 7}, slab_rows < 0, a null or unaligned (16 bytes) pointer, dw and db both
+ *   null, an unknown dtype code.  CPN_E_UNSUPPORTED: more than 2^31 - 1 pixels or weights, more than 65535 tiles of 64 x 64
+ *   channels, a chain longer than 2^31 - 1.  CPN_E_WORKSPACE: a workspace smaller than cpn_resized_conv_wgrad_workspace_bytes =
+ *   slabs * (cin * cout * k * k + cout) * 4.  Every call validates before it reads a pointer.
+ *
+ * Saved for backward: by bilinear_resize the sizes alone, by resized_conv2d x at its low resolution (bf16) and w.  Known limits: T
+ * is written and read once (no footprint sum in the dgrad epilogue); the forward is not decomposed into sub-pixel phases here; the
+ * footprint sums walk a footprint serially in one lane, so a tiny source under a large map (h = w = 1 at the extreme) leaves a
+ * handful of lanes reading the whole image: correct at any ratio, fast at the small ratios of a head; upward resizes only; no
+ * bicubic; no 1 x 1 conv behind a resize.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t cpn_resized_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t h, int32_t w, int32_t cout,
+                                               int32_t k, int32_t slab_rows);
+int cpn_resized_conv_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t k,
+                                int32_t slab_rows, int32_t info[5]);
+int cpn_resized_conv_wgrad(const void *x, const void *dy, int32_t N, int32_t H, int32_t W, int32_t cin, int32_t h, int32_t w,
+                           int32_t cout, int32_t k, int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db,
+                           int32_t db_dtype, void *workspace, int64_t workspace_bytes, void *stream);
+int cpn_bilinear_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, void *dst, int32_t h, int32_t w, void *stream);
+int cpn_bilinear_sum_f32(const float *t, int64_t planes, int32_t H, int32_t W, float *dst, int32_t h, int32_t w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
