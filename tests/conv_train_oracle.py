@@ -1,5 +1,5 @@
 """fp64 statements of the trainable convolution (test helper, not a conftest): what csrc/conv_train.hip and
-celldetection_amd/nn.py must compute, written index by index from the "Trainable convolution" section of include/cpn_hip.h.
+celldetection_amd/nn/conv.py must compute, written index by index from the "Trainable convolution" section of include/cpn_hip.h.
 
 * ``pack_forward`` / ``pack_dgrad``: the two record layouts ``cpn_conv2d`` reads;
 * ``dgrad``: the input gradient as the identity states it -- a stride-1 conv of dY with the taps flipped and the channel roles

@@ -1,5 +1,5 @@
 """fp64 statements of the trainable grouped 3x3 convolution (test helper, not a conftest): what csrc/grouped_conv_train.hip and
-the grouped part of celldetection_amd/nn.py must compute, written index by index from the "Trainable grouped convolution" section
+celldetection_amd/nn/grouped.py must compute, written index by index from the "Trainable grouped convolution" section
 of include/cpn_hip.h.
 
 * ``geometry``: bundle width, bundles, groups per bundle and items of a (C, channels per group) pair;

@@ -1,4 +1,4 @@
-"""CPU tests of the trainable batch normalisation (celldetection_amd/nn.py, csrc/batch_norm.hip, csrc/bn_slabs.h): the fp64
+"""CPU tests of the trainable batch normalisation (celldetection_amd/nn/batch_norm.py, csrc/batch_norm.hip, csrc/bn_slabs.h): the fp64
 statements of tests/batch_norm_oracle.py against torch's own autograd, the wrong rules the cases tell apart, the judge of the GPU
 tests on a CPU emulation of the stated arithmetic (and on three wrong ones), the lane mapping on the host under sanitizers, the
 host-side entry points and the Python surface.  Nothing here needs a GPU."""

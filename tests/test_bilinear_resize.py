@@ -1,4 +1,4 @@
-"""CPU tests of the trainable bilinear resize (celldetection_amd/nn.py, csrc/bilinear_train.hip, csrc/bilinear_adjoint.h): the fp64
+"""CPU tests of the trainable bilinear resize (celldetection_amd/nn/resize.py, csrc/bilinear_train.hip, csrc/bilinear_adjoint.h): the fp64
 statements of tests/bilinear_oracle.py against torch's own autograd of the stock expression, the taps against torch's on one-hot
 inputs, the wrong rules the cases tell apart and the judges reject, the index arithmetic on the host under sanitizers, the host-side
 entry points, the Python surface and the core convert on a stand-in core (tests/cpn_core_standin.py) pinned to the stock expression.
@@ -251,7 +251,7 @@ def test_wgrad_info_and_every_launch_refuse_bad_arguments_without_a_gpu():
                       ((None, 3, 4, 4, 16, 2, 2), _lib.E_INVALID), ((16, 3, 4, 4, 18, 2, 2), _lib.E_INVALID)):
         assert lib.cpn_bilinear_sum_f32(*bad, None) == code and 'cpn_bilinear_sum_f32' in lib.cpn_last_error().decode(), bad
     # cpn_conv2d_sized with the bilinear descriptor: the sizes are looked at before any pointer
-    d = nn._resized_desc(32, 32, 3, False)
+    d = nn.resize._resized_desc(32, 32, 3, False)
     args = (ctypes.byref(d), 16, 32, None, 0, None, 0, 16, 32, 2, 4, 4)
     for stored in ((0, 2, 4, 4, 4, 4), (2, 5, 4, 4, 4, 4), (-1, -1, 4, 4, 4, 4)):
         assert lib.cpn_conv2d_sized(*args, (ctypes.c_int32 * 6)(*stored), 16, None, None) == _lib.E_INVALID, stored
@@ -265,7 +265,7 @@ def test_the_conv_kernels_accept_the_bilinear_descriptor(k):
     the selection takes it, and it is the loader's bilinear mode that is selected."""
     assert nn.RESIZED_KERNEL_SIZES == (3, 5, 7)
     for H, W, cin, cout in ((16, 16, 32, 32), (14, 14, 64, 32), (6, 10, 32, 64), (34, 70, 96, 64), (512, 512, 64, 64)):
-        d = nn._resized_desc(cin, cout, k, True)
+        d = nn.resize._resized_desc(cin, cout, k, True)
         assert (d.src1, d.up0, d.up1, d.c0_used, d.cin_b, d.stride, d.pad) == (-1, 2, 0, cin, cin, 1, k // 2)
         mode = _lib.conv_kernel_info(d, _lib.PRECISION_BF16, 2, H, W, cin, 0, 0, cout)[0]
         assert mode == 'BL', (mode, H, W, cin, cout)

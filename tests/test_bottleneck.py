@@ -1,4 +1,4 @@
-"""CPU tests of the trainable bottleneck block (the last part of celldetection_amd/nn.py; csrc/batch_norm.hip,
+"""CPU tests of the trainable bottleneck block (celldetection_amd/nn/blocks.py; csrc/batch_norm.hip,
 csrc/grouped_conv_train.hip, csrc/grouped_conv.h): the fp64 statements of tests/bottleneck_oracle.py against torch's own autograd, the
 wrong rules the cases tell apart, the judge of the GPU tests on a CPU emulation of the stated arithmetic (and on a wrong one), the
 subsample's index arithmetic on the host under sanitizers, the host-side entry points, the Python surface and

@@ -1,4 +1,4 @@
-"""CPU tests of the trainable concat convolution (celldetection_amd/nn.py, csrc/cat_conv_train.hip, csrc/nearest_adjoint.h): the
+"""CPU tests of the trainable concat convolution (celldetection_amd/nn/cat_conv.py, csrc/cat_conv_train.hip, csrc/nearest_adjoint.h): the
 fp64 statements of tests/cat_conv_oracle.py against torch's own autograd of the stock expression, the wrong rules the cases tell
 apart, the index arithmetic on the host under sanitizers, the host-side entry points, the Python surface and the decoder convert on
 a stand-in decoder (tests/unet_standin.py) pinned to the oracle's restatement of the reference.  Nothing here needs a GPU."""
@@ -203,7 +203,7 @@ def test_wgrad_info_and_every_launch_refuse_bad_arguments_without_a_gpu():
                       ((16, 2, 4, 4, 32, 24, 2, 2), _lib.E_INVALID)):
         assert lib.cpn_nearest_sum(*bad, None) == code and 'cpn_nearest_sum' in lib.cpn_last_error().decode(), bad
     # cpn_conv2d_sized: the sizes are looked at before any pointer
-    d = nn._cat_desc(32, 32, 32, 3, False)
+    d = nn.cat_conv._cat_desc(32, 32, 32, 3, False)
     args = (ctypes.byref(d), 16, 32, 16, 32, None, 0, 16, 32, 2, 4, 4)
     assert lib.cpn_conv2d_sized(*args, None, 16, None, None) == _lib.E_INVALID
     for stored in ((4, 4, 0, 2, 4, 4), (4, 4, 2, 5, 4, 4), (4, 4, -1, -1, 4, 4)):
@@ -220,12 +220,12 @@ def test_the_conv_kernels_accept_the_two_source_descriptor(k):
     assert nn.CAT_KERNEL_SIZES == (1, 3, 5, 7)
     for H, W, c0, c1, cout in ((6, 8, 32, 32, 32), (5, 7, 32, 64, 64), (9, 10, 64, 32, 32), (3, 40, 32, 32, 64), (17, 33, 96, 32, 160),
                                (17, 33, 32, 96, 64)):
-        d = nn._cat_desc(c0, c1, cout, k, True)
+        d = nn.cat_conv._cat_desc(c0, c1, cout, k, True)
         assert (d.src1 >= 0, d.up1, d.up0, d.c0_used, d.cin_b) == (True, 1, 0, c0, c0 + c1)
         mode = _lib.conv_kernel_info(d, _lib.PRECISION_BF16, 2, H, W, c0, c1, 0, cout)[0]
         assert mode == ('PW' if k == 1 else 'S1')
     for h, w, c1, cout in ((1, 1, 32, 32), (3, 5, 64, 32), (17, 20, 32, 64)):
-        d = nn._cat_desc(0, c1, cout, k, False)
+        d = nn.cat_conv._cat_desc(0, c1, cout, k, False)
         assert (d.src1, d.up0, d.up1, d.c0_used) == (-1, 1, 0, c1)
         _lib.conv_kernel_info(d, _lib.PRECISION_BF16, 2, 2 * h, 2 * w, c1, 0, 0, cout)
 

@@ -1,4 +1,4 @@
-"""CPU tests of the trainable convolution (celldetection_amd/nn.py, csrc/conv_train.hip, csrc/wgrad_slabs.h): the fp64 statements
+"""CPU tests of the trainable convolution (celldetection_amd/nn/conv.py, csrc/conv_train.hip, csrc/wgrad_slabs.h): the fp64 statements
 of tests/conv_train_oracle.py against torch's own autograd, the wrong rules the cases tell apart, the slab partition on the host
 under sanitizers, the host-side entry points and the Python surface.  Nothing here needs a GPU."""
 import ctypes

@@ -183,7 +183,7 @@ def test_forward_and_gradients_within_the_bounds(case):
     r = cb.check(f'forward {case}', y.detach().float().cpu(), *cb.bf16_bounds(ref, d), ref, S)
     y.backward(o['dy'].cuda())
     # T, the gradient at size, as the backward computed it (the same deterministic call), by the conv rule; dx on that T
-    t = nn._run_conv(nn._nhwc(o['dy'].cuda(), torch.bfloat16), nn.pack_weight(wt.detach(), 'dgrad'), None, cout, c, k)
+    t = nn._common._run_conv(nn._common._nhwc(o['dy'].cuda(), torch.bfloat16), nn.pack_weight(wt.detach(), 'dgrad'), None, cout, c, k)
     ref, S, d = o['top']
     r2 = cb.check(f'T {case}', t.float().cpu(), *cb.bf16_bounds(ref, d), ref, S)
     assert x.grad.dtype == torch.float32 and x.grad.shape == x.shape
@@ -275,8 +275,8 @@ def test_one_hot_operands_read_the_virtual_operand_out_of_each_route(shape):
     assert torch.equal(forward_operand(x, (h, w), c), x)
     one_hot = torch.zeros(c, c, 3, 3)
     one_hot[torch.arange(c), torch.arange(c), 1, 1] = 1.
-    xs = nn._nhwc(x.cuda(), torch.bfloat16)
-    assert torch.equal(nn._run_resized_conv(xs, nn.pack_weight(one_hot.cuda(), 'forward'), None, c, c, 3, (h, w)).float().cpu(), x)
+    xs = nn._common._nhwc(x.cuda(), torch.bfloat16)
+    assert torch.equal(nn.resize._run_resized_conv(xs, nn.pack_weight(one_hot.cuda(), 'forward'), None, c, c, 3, (h, w)).float().cpu(), x)
 
 
 def test_huge_values_outside_the_tensors_never_reach_a_result():
@@ -345,10 +345,10 @@ def test_layouts_dtypes_and_requested_gradients(monkeypatch):
     assert all(same_bits(p, q) for p, q in zip(base, run(x32.to(torch.bfloat16), wt, b, wide[..., ::2], (H, W))))
     # only the requested gradients are returned, and a kernel whose gradient is not asked for is not run
     calls = []
-    real_conv, real_sum, real_wgrad = nn._run_conv, nn.bilinear_resize_backward, nn.resized_conv2d_weight_grad
-    monkeypatch.setattr(nn, '_run_conv', lambda *a, **kw: (calls.append(('conv', a[4])), real_conv(*a, **kw))[1])  # (a[4]: channels out)
-    monkeypatch.setattr(nn, 'bilinear_resize_backward', lambda *a, **kw: (calls.append(('sum',)), real_sum(*a, **kw))[1])
-    monkeypatch.setattr(nn, 'resized_conv2d_weight_grad', lambda *a, **kw: (calls.append(('wgrad', kw['weight'], kw['bias'])),
+    real_conv, real_sum, real_wgrad = nn.resize._run_conv, nn.resize.bilinear_resize_backward, nn.resize.resized_conv2d_weight_grad
+    monkeypatch.setattr(nn.resize, '_run_conv', lambda *a, **kw: (calls.append(('conv', a[4])), real_conv(*a, **kw))[1])  # (a[4]: channels out)
+    monkeypatch.setattr(nn.resize, 'bilinear_resize_backward', lambda *a, **kw: (calls.append(('sum',)), real_sum(*a, **kw))[1])
+    monkeypatch.setattr(nn.resize, 'resized_conv2d_weight_grad', lambda *a, **kw: (calls.append(('wgrad', kw['weight'], kw['bias'])),
                                                                             real_wgrad(*a, **kw))[1])
     for need in ((True, True, True), (False, True, True), (True, False, True), (True, True, False), (True, False, False),
                  (False, True, False), (False, False, True)):
@@ -482,7 +482,7 @@ def test_converted_core_chain_from_label_images():
             assert same_bits(conv.weight.grad, dw) and same_bits(conv.bias.grad, db)
             info = nn.resized_weight_grad_info(N, H, W, 32, (H // 2, W // 2), 32, 7)
             oracle.check_wgrad('chain: dW', dw, x, dy.float().cpu(), 7, info['steps'] + 2 + info['reduce_chain'])
-            t = nn._run_conv(nn._nhwc(dy, torch.bfloat16), nn.pack_weight(conv.weight.detach(), 'dgrad'), None, 32, 32, 7)
+            t = nn._common._run_conv(nn._common._nhwc(dy, torch.bfloat16), nn.pack_weight(conv.weight.detach(), 'dgrad'), None, 32, 32, 7)
             assert same_bits(seen['dx'].to(torch.bfloat16), nn.bilinear_resize_backward(t, (H // 2, W // 2)))
             oracle.check_adjoint('chain: dx', seen['dx'].float().cpu(), t.float().cpu(), (H // 2, W // 2))
         else:  # (b)

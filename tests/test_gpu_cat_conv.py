@@ -283,10 +283,10 @@ def test_layouts_dtypes_and_requested_gradients(monkeypatch):
     assert all(same_bits(p, q) for p, q in zip(base, run(lat32.to(torch.bfloat16), top32.to(torch.bfloat16), wt, b, perm)))
     # only the requested gradients are returned, and a conv whose gradient is not asked for is not run
     calls = []
-    real_conv, real_sum, real_wgrad = nn._run_conv, nn.nearest_resize_backward, nn.cat_conv2d_weight_grad
-    monkeypatch.setattr(nn, '_run_conv', lambda *a, **kw: (calls.append(('conv', a[4])), real_conv(*a, **kw))[1])  # (a[4]: channels out)
-    monkeypatch.setattr(nn, 'nearest_resize_backward', lambda *a, **kw: (calls.append(('sum',)), real_sum(*a, **kw))[1])
-    monkeypatch.setattr(nn, 'cat_conv2d_weight_grad', lambda *a, **kw: (calls.append(('wgrad', kw['weight'], kw['bias'])),
+    real_conv, real_sum, real_wgrad = nn.cat_conv._run_conv, nn.cat_conv.nearest_resize_backward, nn.cat_conv.cat_conv2d_weight_grad
+    monkeypatch.setattr(nn.cat_conv, '_run_conv', lambda *a, **kw: (calls.append(('conv', a[4])), real_conv(*a, **kw))[1])  # (a[4]: channels out)
+    monkeypatch.setattr(nn.cat_conv, 'nearest_resize_backward', lambda *a, **kw: (calls.append(('sum',)), real_sum(*a, **kw))[1])
+    monkeypatch.setattr(nn.cat_conv, 'cat_conv2d_weight_grad', lambda *a, **kw: (calls.append(('wgrad', kw['weight'], kw['bias'])),
                                                                         real_wgrad(*a, **kw))[1])
     for need in ((False, True, True, True), (True, False, True, True), (True, True, False, True), (True, True, True, False),
                  (False, False, True, False), (True, False, False, False), (False, True, False, False), (False, False, False, True)):

@@ -244,6 +244,30 @@ def test_layouts_dtypes_and_requested_gradients():
         nn.conv2d(x32.cpu(), wt.cpu(), b.cpu())
 
 
+def test_a_view_that_starts_off_a_16_byte_address_gives_the_bits_of_its_clone():
+    """A channels-last bf16 view one element into a buffer: the kernels' 16-byte loads only ever see the aligned clone ``_nhwc``
+    makes of it, so output and all three gradients are those of ``view.clone()`` bit for bit."""
+    n, c, h, w, k = 1, 32, 4, 5, 3
+    g = torch.Generator().manual_seed(5)
+    buf = torch.randn(n * h * w * c + 1, generator=g).to(torch.bfloat16).cuda()
+    view = buf[1:].view(n, h, w, c).permute(0, 3, 1, 2)
+    assert view.is_contiguous(memory_format=torch.channels_last) and view.data_ptr() % 16 == 2
+    wt, b = torch.randn(c, c, k, k, generator=g).cuda(), torch.randn(c, generator=g).cuda()
+    dy = torch.randn(n, c, h, w, generator=g).to(torch.bfloat16).cuda()
+
+    def run(x):  # (run_conv2d clones x, which would align it)
+        x, wp, bp = x.detach().requires_grad_(True), wt.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        y = nn.conv2d(x, wp, bp)
+        y.backward(dy)
+        return y.detach(), x.grad, wp.grad, bp.grad
+
+    aligned = view.clone()
+    assert aligned.data_ptr() % 16 == 0 and torch.equal(aligned, view)
+    got, ref = run(view), run(aligned)
+    for name, p, q in zip(('y', 'dx', 'dw', 'db'), got, ref):
+        assert same_bits(p, q) and torch.equal(p, q), name
+
+
 def test_module_is_a_drop_in_for_torch_conv2d():
     torch.manual_seed(0)
     stock = torch.nn.Conv2d(32, 64, 5, padding=2).cuda()

@@ -1,4 +1,4 @@
-"""CPU tests of the trainable grouped 3x3 convolution (the grouped part of celldetection_amd/nn.py, csrc/grouped_conv_train.hip,
+"""CPU tests of the trainable grouped 3x3 convolution (celldetection_amd/nn/grouped.py, csrc/grouped_conv_train.hip,
 csrc/grouped_conv.h): the fp64 statements of tests/grouped_conv_oracle.py against torch's own autograd, the stride-2 identity, the
 wrong rules the cases tell apart, the index arithmetic on the host under sanitizers, the host-side entry points and the Python
 surface.  Nothing here needs a GPU."""
@@ -213,16 +213,16 @@ def test_cpn_conv2d_accepts_every_descriptor_of_the_family():
     at stride 1 and 2 and the dgrad descriptor of every GPU test shape and of the encoder's shapes, and names a kernel for it."""
     shapes = GPU_SHAPES + [(8, 128, 128, 256, 8), (8, 64, 64, 512, 16), (8, 32, 32, 1024, 32), (8, 16, 16, 2048, 64), (8, 128, 128, 128, 4)]
     for (n, h, w, c, cig), stride in itertools.product(shapes, (1, 2)):
-        assert nn._grouped_channels(c, c, c // cig) is None
-        d = nn._grouped_desc(c, cig, stride, True)
+        assert nn.grouped._grouped_channels(c, c, c // cig) is None
+        d = nn.grouped._grouped_desc(c, cig, stride, True)
         assert (d.bundles, d.cin_b, d.cout_b) == oracle.geometry(c, cig)[1::-1] + (oracle.geometry(c, cig)[0],)
         mode = _lib.conv_kernel_info(d, _lib.PRECISION_BF16, n, h, w, c, dst_stride=c)[0]
         assert mode in (('S1', 'N', 'S1F', 'S1Q') if stride == 1 else ('S2',)), (n, h, w, c, cig, stride, mode)
-        _lib.conv_kernel_info(nn._grouped_desc(c, cig, 1, False), _lib.PRECISION_BF16, n, h, w, c, dst_stride=c)
+        _lib.conv_kernel_info(nn.grouped._grouped_desc(c, cig, 1, False), _lib.PRECISION_BF16, n, h, w, c, dst_stride=c)
     # ... and what the predicate rejects, the host entry rejects
     out = (ctypes.c_int32 * 5)()
     for c, cig in ((48, 16), (96, 64), (64, 2), (256, 128), (16, 4), (0, 4)):
-        assert nn._grouped_channels(c, c, c // cig if c else 1) is not None
+        assert nn.grouped._grouped_channels(c, c, c // cig if c else 1) is not None
         assert _lib.load().cpn_grouped_conv_wgrad_info(1, 4, 4, c, cig, 1, 0, out) == _lib.E_INVALID
 
 

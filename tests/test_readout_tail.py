@@ -1,4 +1,4 @@
-"""CPU tests of the trainable ReadOut tail (celldetection_amd/nn.py, csrc/readout_tail.hip, csrc/tail_slabs.h): the fp64 statements
+"""CPU tests of the trainable ReadOut tail (celldetection_amd/nn/readout_tail.py, csrc/readout_tail.hip, csrc/tail_slabs.h): the fp64 statements
 of tests/readout_tail_oracle.py against torch's own autograd, the wrong rules the cases tell apart, the partitions on the host
 under sanitizers, the host-side entry points, the Python surface and ``convert_readout_tail_``.  Nothing here needs a GPU."""
 import ctypes

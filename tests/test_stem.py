@@ -1,4 +1,4 @@
-"""CPU tests of the trainable stem and max-pool (celldetection_amd/nn.py, csrc/stem_train.hip, csrc/pool_adjoint.h): the fp64
+"""CPU tests of the trainable stem and max-pool (celldetection_amd/nn/stem.py, nn/pool.py, csrc/stem_train.hip, csrc/pool_adjoint.h): the fp64
 statements of tests/stem_oracle.py against torch's own float64 results, the wrong rules the cases tell apart, the pool's index
 arithmetic and the stem's staging on the host under sanitizers, the host-side entry points, the Python surface and the two converts
 on stand-ins with the reference's layout.  Nothing here needs a GPU."""

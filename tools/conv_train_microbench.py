@@ -67,8 +67,8 @@ def bench_shape(name, n, h, w, cin, cout, k, rounds, reps):
 
     calls = {
         'pack': lambda: (nn.pack_weight(wt, 'forward'), nn.pack_weight(wt, 'dgrad')),
-        'forward': lambda: nn._run_conv(x, pf, b32, cin, cout, k),
-        'dgrad': lambda: nn._run_conv(dy, pd, None, cout, cin, k),
+        'forward': lambda: nn._common._run_conv(x, pf, b32, cin, cout, k),
+        'dgrad': lambda: nn._common._run_conv(dy, pd, None, cout, cin, k),
         'wgrad': lambda: nn.conv2d_weight_grad(x, dy, k),
         'step': ours_step,
         'stock forward': stock_forward,
@@ -85,7 +85,7 @@ def bench_shape(name, n, h, w, cin, cout, k, rounds, reps):
     med = {key: statistics.median(v) for key, v in times.items()}
     spread = {key: (min(v), max(v)) for key, v in times.items()}
     # same operands, same results (bf16 outputs against each other; the gradients against the stock bf16 ones)
-    y_ours = nn._run_conv(x, pf, b32, cin, cout, k).float()
+    y_ours = nn._common._run_conv(x, pf, b32, cin, cout, k).float()
     stock_forward()
     rel = float((y_ours - state['y'].detach().float()).abs().max() / state['y'].detach().float().abs().max())
     flop = 2. * n * h * w * cin * cout * k * k

@@ -81,8 +81,8 @@ def bench_shape(name, n, h, w, c, stride, rounds, reps):
 
     calls = {
         'pack': lambda: (nn.grouped_pack_weight(wt, GROUPS, 'forward'), nn.grouped_pack_weight(wt, GROUPS, 'dgrad')),
-        'forward': lambda: nn._run_grouped(x, pf, b32, c, cig, stride),
-        'dx': lambda: nn._run_grouped(dz, pd, None, c, cig, 1),
+        'forward': lambda: nn.grouped._run_grouped(x, pf, b32, c, cig, stride),
+        'dx': lambda: nn.grouped._run_grouped(dz, pd, None, c, cig, 1),
         'dW': lambda: nn.grouped_conv2d_weight_grad(x, dy, GROUPS, stride, dilated=dz),
         'step': ours_step,
         'stock forward': stock_forward,
@@ -104,7 +104,7 @@ def bench_shape(name, n, h, w, c, stride, rounds, reps):
     med = {key: statistics.median(v) for key, v in times.items()}
     spread = {key: (min(v), max(v)) for key, v in times.items()}
     # same operands, same results (bf16 outputs against each other)
-    y_ours = nn._run_grouped(x, pf, b32, c, cig, stride).float()
+    y_ours = nn.grouped._run_grouped(x, pf, b32, c, cig, stride).float()
     stock_forward()
     rel = float((y_ours - state['y'].detach().float()).abs().max() / state['y'].detach().float().abs().max())
     flop = 2. * n * ho * wo * c * cig * 9

@@ -110,12 +110,12 @@ def conv_shape(n, c, cout, k, low, high, repeats):
         xs, gs = x.detach(), dy
         packed_f, packed_d = nn.pack_weight(w, 'forward'), nn.pack_weight(w, 'dgrad')
         b32 = b.detach().float()
-        t = nn._run_conv(gs, packed_d, None, cout, c, k)
+        t = nn._common._run_conv(gs, packed_d, None, cout, c, k)
         big = nn.bilinear_resize(xs, size)
         kernels = {
-            'forward (loader blends)': lambda: nn._run_resized_conv(xs, packed_f, b32, c, cout, k, size),
-            'forward, dense conv on a materialised resize': lambda: nn._run_conv(big, packed_f, b32, c, cout, k),
-            'dgrad conv (T)': lambda: nn._run_conv(gs, packed_d, None, cout, c, k),
+            'forward (loader blends)': lambda: nn.resize._run_resized_conv(xs, packed_f, b32, c, cout, k, size),
+            'forward, dense conv on a materialised resize': lambda: nn._common._run_conv(big, packed_f, b32, c, cout, k),
+            'dgrad conv (T)': lambda: nn._common._run_conv(gs, packed_d, None, cout, c, k),
             'bilinear_sum (T -> dx)': lambda: nn.bilinear_resize_backward(t, (low, low)),
             'weight gradient (staging blends)': lambda: nn.resized_conv2d_weight_grad(xs, gs, k),
             'weight gradient, dense on a materialised resize': lambda: nn.conv2d_weight_grad(big, gs, k),

@@ -97,13 +97,13 @@ def bench_stem(n, size, rounds, reps, out):
     for name, fn in list(versions.items())[:2]:
         out(f'  peak memory above the operands, {name}: {peak_above_operands(fn):.1f} MiB')
     # each launch alone
-    xp = nn._stem_pad(x)
+    xp = nn.stem._stem_pad(x)
     packed = nn.stem_pack_weight(w)
     gs = dy
-    pieces = {'pad + convert the input': (lambda: nn._stem_pad(x), x.numel() * 4 + xp.numel() * 2),
+    pieces = {'pad + convert the input': (lambda: nn.stem._stem_pad(x), x.numel() * 4 + xp.numel() * 2),
               'pack the weight': (lambda: nn.stem_pack_weight(w), w.numel() * 4 + packed.numel() * 2),
-              'forward kernel': (lambda: nn._stem_forward(xp, (n, size, size), packed, None), xp.numel() * 2 + dy.numel() * 2),
-              'weight gradient (slabs + reduce)': (lambda: nn._stem_wgrad(xp, (n, size, size), 3, gs, 0, True, False, torch.float32, torch.float32),
+              'forward kernel': (lambda: nn.stem._stem_forward(xp, (n, size, size), packed, None), xp.numel() * 2 + dy.numel() * 2),
+              'weight gradient (slabs + reduce)': (lambda: nn.stem._stem_wgrad(xp, (n, size, size), 3, gs, 0, True, False, torch.float32, torch.float32),
                                                    xp.numel() * 2 + dy.numel() * 2)}
     for name, (fn, nbytes) in pieces.items():
         t = alternate({name: fn}, rounds, reps)[name]
