@@ -10,7 +10,7 @@
 //   gc_subsample_kernel:   the gather back, xs[i][j] = x[2 i][2 j], 16 bytes per lane: the operand of the strided 1x1 shortcut's
 //                          weight gradient (cpn_subsample2d, "Trainable bottleneck block" of include/cpn_hip.h).
 // Weight gradient, dW[co][cl][ky][kx] = sum over pixels p of dZ[p][co] * X[p + (ky - 1) * W + (kx - 1)][g(co) * cig + cl]:
-//   gc_wgrad_slab_kernel:  the method of ct_wgrad_slab_kernel (csrc/conv_train.hip) on the diagonal fragments only.  One workgroup =
+//   gc_wgrad_slab_kernel:  the method of ct_wgrad_slab_kernel (csrc/wgrad_dense.h) on the diagonal fragments only.  One workgroup =
 //                          (slab of the pixel range, span of four fragments, filter row ky); a wave owns ONE diagonal 32 x 32
 //                          fragment and three accumulators of it (one per kx).  Per chunk of 64 pixels it stages the dZ rows of
 //                          the span's 32-channel chunks and the X rows of the flat range

@@ -18,7 +18,7 @@
 //                               i % 4 of the 32-channel tile, so that a lane's 16 registers are 16 CONSECUTIVE channels of its
 //                               pixel: 32 bytes of dx, two 16-byte stores.
 //                          dW:  D[o][c] = G[o][pixel] x[pixel][c], K = the slab's pixels, 16 per step; A is 16 bytes of a G row, B the
-//                               staged x through the transposed LDS read (ds_read_b64_tr_b16), as ct_wgrad_slab_kernel does.  Wave w
+//                               staged x through the transposed LDS read (ds_read_b64_tr_b16), as csrc/wgrad_dense.h does.  Wave w
 //                               owns the channel tiles w, w + 4, ...: one fp32 accumulator per element for the whole slab, written
 //                               to workspace[slab][o][c].
 //                          db:  eight interleaved chains per channel over G, added in order, to workspace[slabs ...][slab][o].

@@ -455,11 +455,7 @@ int cpn_stem_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cout, int32_t s
     WgSlabs part;
     if (const int rc = st_check("cpn_stem_wgrad_info", N, H, W, cout, slab_rows, &part)) return rc;
     if (!info) return cpn::fail(CPN_E_INVALID, "cpn_stem_wgrad_info: null pointer");
-    info[0] = part.slabs;
-    info[1] = part.slab_rows;
-    info[2] = part.steps;
-    info[3] = part.slabs;  // the reduce chain: one add per slab
-    info[4] = (int32_t) wgs_bias_chain(part);
+    wgs_info(part, info);
     return 0;
 }
 

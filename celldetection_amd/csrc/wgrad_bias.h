@@ -1,4 +1,4 @@
-// The bias gradient of the trainable convs and the bf16 rounding they share (csrc/conv_train.hip, csrc/grouped_conv_train.hip):
+// The bias gradient of the trainable convs and the bf16 rounding they share (csrc/wgrad_dense.h, csrc/grouped_conv_train.hip):
 //   ct_bias_slab_kernel / ct_bias_reduce_kernel: sum of dY per channel, eight interleaved chains per slab added in order, then the
 //   slabs in ascending order.  No floating-point atomics.  The partition is csrc/wgrad_slabs.h.
 // Device code with internal linkage: every unit that includes this header gets its own copy.

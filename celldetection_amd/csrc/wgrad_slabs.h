@@ -1,4 +1,4 @@
-// The slab partition of the weight-gradient reduction (csrc/conv_train.hip).  The reduction index of dW is the pixel
+// The slab partition of the weight-gradient reduction (csrc/wgrad_dense.h).  The reduction index of dW is the pixel
 // p = (n * H + y) * W + x of the NHWC tensors; R = N * H image rows of W pixels each.  A slab is `slab_rows` consecutive image rows
 // (the last slab may be partial; a slab may cross from one image of the batch into the next), i.e. the pixel range
 // [s * slab_rows * W, min(R, (s + 1) * slab_rows) * W).  A workgroup reduces the pixels of its slab in ascending order, 16 per MFMA
@@ -64,4 +64,14 @@ WGS_HD int64_t wgs_chain(const WgSlabs &s) { return (int64_t) s.steps + 2 + s.sl
 // ... and of one bias-gradient element: ceil(slab pixels / 8) adds per interleaved chain, 8 adds across them, one per slab
 WGS_HD int64_t wgs_bias_chain(const WgSlabs &s) {
     return wgs_ceil_div((int64_t) s.slab_rows * s.W, WGS_BIAS_LANES) + WGS_BIAS_LANES + s.slabs;
+}
+
+// the five numbers of a *_wgrad_info call: slabs, rows per slab, MFMA steps of the largest slab, and the two chains that the slabs
+// add to it -- the reduce chain (one add per slab) and the bias chain
+WGS_HD void wgs_info(const WgSlabs &s, int32_t info[5]) {
+    info[0] = s.slabs;
+    info[1] = s.slab_rows;
+    info[2] = s.steps;
+    info[3] = s.slabs;
+    info[4] = (int32_t) wgs_bias_chain(s);
 }

@@ -976,7 +976,8 @@ int cpn_components_label(const int32_t *in, int64_t pixel_stride, int64_t channe
 
 /* ---- Trainable convolution ---------------------------------------------------------------------------------
  * What celldetection_amd.nn.conv2d needs besides cpn_conv2d to train a dense stride-1 convolution (csrc/conv_train.hip,
- * csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
+ * csrc/wgrad_dense.h -- the one weight-gradient kernel of this section, of "Trainable concat convolution" and of "Trainable bilinear
+ * resize" --, csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
  *
  * The rule.  Supported: groups 1, stride 1, dilation 1, a square odd kernel k in {1, 3, 5, 7}, zero padding k / 2, cin and cout
  * positive multiples of 32.  Activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32,
@@ -1242,8 +1243,8 @@ int cpn_subsample2d(const void *x, int32_t N, int32_t Hin, int32_t Win, int32_t 
 
 /* ---- Trainable concat convolution ---------------------------------------------------------------------------
  * What celldetection_amd.nn.cat_conv2d needs besides cpn_conv2d and the "Trainable convolution" section to train the first conv
- * of a U-Net decoder level (csrc/cat_conv_train.hip, csrc/nearest_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to
- * ABI 22.  This text is the contract.
+ * of a U-Net decoder level (csrc/cat_conv_train.hip, csrc/nearest_adjoint.h, csrc/wgrad_dense.h, csrc/wgrad_slabs.h,
+ * csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
  *
  * The function.  y = conv(cat(x0, R(x1)), w) + b with x0 [N][H][W][C0] (the lateral) first and x1 [N][h][w][C1] (the top) second,
  * 1 <= h <= H, 1 <= w <= W, bf16 NHWC; w [cout][C0 + C1][k][k], k square and odd, stride 1, padding k / 2 with zeros; C0, C1 and
@@ -1383,7 +1384,8 @@ int cpn_maxpool2d_backward(const void *dy, const void *index, int32_t dtype, int
  * What celldetection_amd.nn.bilinear_resize and nn.resized_conv2d need besides cpn_resize_bilinear, cpn_resize_bilinear_f32,
  * cpn_conv2d_sized and the "Trainable convolution" section to train the refinement head of a CPN: the resize of the refinement
  * features to the input's size in front of the head's k x k conv, and the resize of the head maps (csrc/bilinear_train.hip,
- * csrc/bilinear_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
+ * csrc/bilinear_adjoint.h, csrc/wgrad_dense.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the
+ * contract.
  *
  * The map.  B is F.interpolate(mode='bilinear', align_corners=False) from h x w to H x W, 1 <= h <= H, 1 <= w <= W.  Per axis,
  * output index dst reads

@@ -291,8 +291,11 @@ def test_header_binding_and_exports_agree():
             'resized_conv2d_weight_grad', 'resized_weight_grad_info'} <= set(nn.__all__)
     assert all(hasattr(nn, name) for name in nn.__all__)
     src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'bilinear_train.hip')).read()
-    assert 'atomic' not in src.replace('No floating-point atomics', '') and 'fmaf' not in src and 'fma(' not in src
-    assert 'ds_read_tr16_b64' in src and 'mfma_f32_32x32x16_bf16' in src and 'ba_tap' in src and 'ba_first' in src
+    dense = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'wgrad_dense.h')).read()  # the slab kernel, compiled inside the unit
+    assert '#include "wgrad_dense.h"' in src and 'wgrad_dense.h' in build.HEADERS
+    for text in (src, dense):
+        assert 'atomic' not in text.replace('No floating-point atomics', '') and 'fmaf' not in text and 'fma(' not in text
+    assert 'ds_read_tr16_b64' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'ba_tap' in src and 'ba_first' in src
     adj = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'bilinear_adjoint.h')).read()
     assert 'fmaxf(scale * ((float) dst + 0.5f) - 0.5f, 0.f)' in adj and '*i0 + (*i0 < in_size - 1)' in adj
     assert 'fmaxf(fmaf(scale, (float) dst + 0.5f, -0.5f), 0.f)' in adj

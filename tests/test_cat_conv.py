@@ -247,8 +247,11 @@ def test_header_binding_and_exports_agree():
     assert 'cat_conv_train.hip' in build.SOURCES and 'nearest_adjoint.h' in build.HEADERS
     assert {'cat_conv2d', 'CatConv2d', 'UNetDecoder', 'convert_unet_decoder_', 'nearest_resize_backward'} <= set(nn.__all__)
     src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'cat_conv_train.hip')).read()
-    assert 'conv_igemm_kernel' not in src and 'atomic' not in src.replace('No floating-point atomics', '')
-    assert 'ds_read_tr16_b64' in src and 'mfma_f32_32x32x16_bf16' in src
+    dense = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'wgrad_dense.h')).read()  # the slab kernel, compiled inside the unit
+    assert '#include "wgrad_dense.h"' in src and 'wgrad_dense.h' in build.HEADERS
+    for text in (src, dense):
+        assert 'conv_igemm_kernel' not in text and 'atomic' not in text.replace('No floating-point atomics', '')
+    assert 'ds_read_tr16_b64' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'na_pixel_src' in src
     for doc in ('README.md', 'DESIGN.md', 'INTEGRATION.md'):
         assert 'cat_conv2d' in open(os.path.join(ROOT, doc)).read(), doc
 

@@ -179,6 +179,59 @@ def test_weight_gradient_is_bit_identical_from_run_to_run_and_rounds_once():
     assert only_w[1] is None and only_b[0] is None and same_bits(only_w[0], dw) and same_bits(only_b[1], db)
 
 
+# ---- one slab kernel, three sources (csrc/wgrad_dense.h): at an identity map the gathered and the blended rows ARE the rows of the
+# materialised tensor, and the partitions coincide, so the routes agree with the dense one bit for bit
+
+IDENTITY_HW = (5, 7)
+
+
+def same_partition(a, b):
+    assert a == b, (a, b)
+    return a
+
+
+@pytest.mark.parametrize('slab_rows', [1, 0])
+@pytest.mark.parametrize('k', [1, 3])
+@pytest.mark.parametrize('c1', [32, 64])
+def test_concat_route_at_an_identity_map_is_the_dense_route_bit_for_bit(c1, k, slab_rows):
+    H, W = IDENTITY_HW
+    c0 = cout = 32
+    lateral, top = bf16_exact(N, c0, H, W, seed=300 + c1 + k).cuda(), bf16_exact(N, c1, H, W, seed=400 + c1 + k).cuda()
+    dy = bf16_exact(N, cout, H, W, seed=500 + c1 + k).cuda()
+    info = same_partition(nn.cat_weight_grad_info(N, H, W, c0, c1, (H, W), cout, k, slab_rows),
+                          nn.weight_grad_info(N, H, W, c0 + c1, cout, k, slab_rows))
+    assert slab_rows == 0 or info['slabs'] == N * H
+    assert bool(torch.isfinite(lateral).all() and torch.isfinite(top).all() and torch.isfinite(dy).all())
+    dw, db = nn.cat_conv2d_weight_grad(lateral, top, dy, k, slab_rows)
+    dw_dense, db_dense = nn.conv2d_weight_grad(torch.cat((lateral, top), 1), dy, k, slab_rows)
+    assert same_bits(dw, dw_dense) and same_bits(db, db_dense), (c1, k, slab_rows, info)
+    if slab_rows == 0:  # ... and as autograd calls them: nn.cat_conv2d against nn.conv2d on the materialised concat
+        wt, b = bf16_exact(cout, c0 + c1, k, k, seed=600 + c1 + k, scale=.1).cuda(), bf16_exact(cout, seed=700 + c1 + k).cuda()
+        grads = []
+        for conv in (lambda w_, b_: nn.cat_conv2d(lateral, top, w_, b_), lambda w_, b_: nn.conv2d(torch.cat((lateral, top), 1), w_, b_)):
+            w_, b_ = wt.clone().requires_grad_(True), b.clone().requires_grad_(True)
+            conv(w_, b_).backward(dy)
+            grads.append((w_.grad, b_.grad))
+        assert same_bits(grads[0][0], grads[1][0]) and same_bits(grads[0][1], grads[1][1]) and same_bits(grads[0][0], dw)
+
+
+@pytest.mark.parametrize('slab_rows', [1, 0])
+@pytest.mark.parametrize('k', [3, 7])
+@pytest.mark.parametrize('c', [32, 96])
+def test_resized_route_at_an_identity_map_is_the_dense_route_bit_for_bit(c, k, slab_rows):
+    """both lambdas are 0 at equal sizes: the blend is 1 * (1 * a + 0 * b) + 0 * (...) = a on finite values"""
+    H, W = IDENTITY_HW
+    cout = 32
+    x, dy = bf16_exact(N, c, H, W, seed=100 + c + k).cuda(), bf16_exact(N, cout, H, W, seed=200 + c + k).cuda()
+    info = same_partition(nn.resized_weight_grad_info(N, H, W, c, (H, W), cout, k, slab_rows),
+                          nn.weight_grad_info(N, H, W, c, cout, k, slab_rows))
+    assert slab_rows == 0 or info['slabs'] == N * H
+    assert bool(torch.isfinite(x).all() and torch.isfinite(dy).all())
+    dw, db = nn.resized_conv2d_weight_grad(x, dy, k, slab_rows)
+    dw_dense, db_dense = nn.conv2d_weight_grad(x, dy, k, slab_rows)
+    assert same_bits(dw, dw_dense) and same_bits(db, db_dense), (c, k, slab_rows, info)
+
+
 # ---- the adjoint of the resize alone, exact
 
 @pytest.mark.parametrize('shape', [(6, 8, 3, 4), (5, 7, 3, 4), (5, 7, 2, 3), (9, 10, 3, 3), (5, 7, 5, 7), (3, 40, 1, 1), (46, 3, 14, 2),
