@@ -56,7 +56,7 @@ SOURCES = {
     # trainable ReadOut tail: Dropout2d + 1x1 conv to few channels, three MFMA products (partition: csrc/tail_slabs.h)
     'readout_tail.hip': [],
     # trainable grouped 3x3 conv: block-diagonal packs, stride-2 dilation, the weight gradient of the diagonal fragments (index
-    # arithmetic: csrc/grouped_conv.h; the bias gradient's kernels: csrc/wgrad_bias.h)
+    # arithmetic: csrc/grouped_conv.h; the slab kernel: csrc/wgrad_dense.h; the bias gradient's kernels: csrc/wgrad_bias.h)
     'grouped_conv_train.hip': [],
     # trainable concat conv of the decoder: the weight gradient over the virtual concat of the lateral and the nearest-resized top,
     # and the adjoint of the resize (index arithmetic: csrc/nearest_adjoint.h)
@@ -76,7 +76,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

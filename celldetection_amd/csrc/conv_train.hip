@@ -5,8 +5,8 @@
 //   ct_pack_kernel:        [Cout][Cin][k][k] fp32 | bf16 -> [item][out channel][32] bf16, forward (item = (chunk of Cin, tap)) or
 //                          dgrad (item = (chunk of Cout, tap), tap flipped, channel roles swapped); one zero item behind an odd count.
 // The weight gradient is csrc/wgrad_dense.h (ct_wgrad_slab_kernel, ct_wgrad_reduce_kernel, the host path around them) with the
-// plainest Source: a staged X row is the row of x as it lies.  The bias gradient is csrc/wgrad_bias.h.  No floating-point atomics:
-// results are bit-identical from run to run.  The partition is csrc/wgrad_slabs.h.
+// plainest Source (CtDense, defined there): a staged X row is the row of x as it lies.  The bias gradient is csrc/wgrad_bias.h.  No
+// floating-point atomics: results are bit-identical from run to run.  The partition is csrc/wgrad_slabs.h.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -41,19 +41,6 @@ __global__ __launch_bounds__(256) void ct_pack_kernel(const void *w, int w_dtype
     }
     packed[o] = v;
 }
-
-// X as it lies: [pixel][Cin]
-struct CtDense {
-    static constexpr int ENTRY = 0, KMIN = 1;
-    const uint16_t *x;
-    int C;
-    __device__ __forceinline__ int channels() const { return C; }
-    __device__ __forceinline__ u32x4 item(const char *, int64_t f, long P, int ch, int q) const {
-        u32x4 v = {0, 0, 0, 0};
-        if (f >= 0 && f < P && ch < C) v = *(const u32x4 *) (x + f * C + ch + q * 8);
-        return v;
-    }
-};
 
 // 0, or the error code with its message recorded; the partition of an accepted call
 int ct_check(const char *who, int N, int H, int W, int cin, int cout, int k, int slab_rows, WgSlabs *part) {

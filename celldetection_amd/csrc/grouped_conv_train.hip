@@ -10,14 +10,11 @@
 //   gc_subsample_kernel:   the gather back, xs[i][j] = x[2 i][2 j], 16 bytes per lane: the operand of the strided 1x1 shortcut's
 //                          weight gradient (cpn_subsample2d, "Trainable bottleneck block" of include/cpn_hip.h).
 // Weight gradient, dW[co][cl][ky][kx] = sum over pixels p of dZ[p][co] * X[p + (ky - 1) * W + (kx - 1)][g(co) * cig + cl]:
-//   gc_wgrad_slab_kernel:  the method of ct_wgrad_slab_kernel (csrc/wgrad_dense.h) on the diagonal fragments only.  One workgroup =
-//                          (slab of the pixel range, span of four fragments, filter row ky); a wave owns ONE diagonal 32 x 32
-//                          fragment and three accumulators of it (one per kx).  Per chunk of 64 pixels it stages the dZ rows of
-//                          the span's 32-channel chunks and the X rows of the flat range
-//                          [chunk + (ky - 1) * W - 1, ... + 64 + 2) in LDS as they lie (64-byte rows), and reads both as operands of
-//                          v_mfma_f32_32x32x16_bf16 with ds_read_b64_tr_b16.  A tap outside the image, or a pixel behind the slab,
-//                          points at a row of zeros: EXEC stays all ones, every address is 8-byte aligned.  Partial sums go to
-//                          workspace[slab][tap][fragment][32 co][32 ci].
+//   ct_wgrad_slab_kernel<3, 1, CtDense, GcSpans>: the slab kernel of csrc/wgrad_dense.h, its text unchanged, on the diagonal
+//                          fragments only; what is the grouped conv's own is the Tiling GcSpans below.  One workgroup = (slab of the
+//                          pixel range, span of four fragments, filter row ky); a wave owns ONE diagonal 32 x 32 fragment and three
+//                          accumulators of it (one per kx); chunks of 64 pixels; x and dZ are staged as they lie (CtDense).
+//                          Partial sums go to workspace[slab][tap][fragment][32 co][32 ci].
 //   gc_wgrad_reduce_kernel: per dW element: the slabs in ascending order (one fp32 chain), rounded once.  It reads only the
 //                          entries whose input and output channel share a group: the off-group products of a 32-wide bundle
 //                          never reach dW.
@@ -32,17 +29,11 @@
 #include "cpn_error.h"
 #include "grouped_conv.h"
 #include "wgrad_bias.h"
+#define WGRAD_SLAB_KERNEL_ONLY  // the slab kernel, CtDense and ct_check_chains; not the dense reduce kernel and host path
+#include "wgrad_dense.h"
 #include "wgrad_slabs.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-constexpr int GC_ROW = 64;  // bytes of an LDS row: 32 channels
-constexpr int GC_NO_TAP = -(1 << 24);
 
 __global__ __launch_bounds__(256) void gc_pack_kernel(const void *w, int w_dtype, GcGeo geo, int dgrad, uint16_t *packed,
                                                        long total) {
@@ -72,106 +63,36 @@ __global__ __launch_bounds__(256) void gc_subsample_kernel(const u32x4 *__restri
     xs[u] = x[gc_subsample_source(u, Hin, Win, C8, stride)];
 }
 
-// LDS image of the slab kernel: dZ [4 blocks][CH rows], X [4 blocks][CH + 2 rows], one row of zeros, the column of every chunk
-// pixel (int32; a large negative number where no tap of this filter row applies).  Every offset is a multiple of 16.
-constexpr int GC_CH = 64;  // pixels per staged chunk (4 MFMA steps)
-struct GcLds {
-    static constexpr int XR = GC_CH + 2;
-    static constexpr int DY = 0, X = DY + 4 * GC_CH * GC_ROW, ZERO = X + 4 * XR * GC_ROW, META = ZERO + GC_ROW, TOTAL = META + GC_CH * 4;
+// The Tiling of ct_wgrad_slab_kernel for the diagonal fragments (the contract is written in csrc/wgrad_dense.h): blockIdx.y = span.
+// A workgroup stages the span's 32-channel chunks of dZ and of X (two or four; chunks behind C hold zeros), wave w multiplies the two
+// chunks of fragment 4 span + w; a wave behind the last fragment multiplies chunk w by chunk w -- zeros, or a product nobody reads
+// -- and stores nothing.  LDS: dZ [4 blocks][64 rows], X [4 blocks][66 rows], the zero row, the column table: 33600 bytes.
+struct GcSpans {
+    static constexpr int CH = 64, FR = 1, DYB = 4, XB = 4;
+    GcGeo geo;
+    struct Tile {
+        int dy_blocks, x_blocks, dy0, x0, a_block, b_block, frag, frags, half, col;
+        template <int K>
+        __device__ __forceinline__ void store(float *ws, int slab, int ky, const f32x16 (&acc)[1][K], int, int) const {
+            if (frag >= 0) {
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) {
+                    float *out = ws + (((int64_t) slab * GCV_TAPS + ky * K + kx) * frags + frag) * 1024 + col;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) out[mf_row(r, half) * 32] = acc[0][kx][r];
+                }
+            }
+        }
+    };
+    __device__ __forceinline__ Tile tile(unsigned span, int wave, int lane) const {
+        const int nb = gc_span_chunks(geo), first = gc_span_first_chunk(geo, (int) span);
+        const int frag = gc_wave_frag(geo, (int) span, wave);  // (wave-uniform)
+        int co_chunk = 0, ci_chunk = 0;
+        gc_frag_chunks(geo, frag < 0 ? 0 : frag, &co_chunk, &ci_chunk);
+        return Tile{nb, nb, first * 32, first * 32, frag < 0 ? wave : co_chunk - first, frag < 0 ? wave : ci_chunk - first, frag,
+                    geo.frags, lane >> 5, lane & 31};
+    }
 };
-
-__device__ __forceinline__ s16x4 gc_read_tr(const char *smem, int byte_offset) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *) (smem + byte_offset));
-}
-
-__global__ __launch_bounds__(256) void gc_wgrad_slab_kernel(const uint16_t *__restrict__ dz, const uint16_t *__restrict__ x,
-                                                             float *__restrict__ ws, WgSlabs part, GcGeo geo, int H, long P) {
-    typedef GcLds L;
-    constexpr int CH = GC_CH;
-    __shared__ __attribute__((aligned(16))) char smem[L::TOTAL];
-    const int tid = threadIdx.x, W = part.W, C = geo.C;
-    const int slab = blockIdx.x, span = blockIdx.y, ky = blockIdx.z;
-    const int NB = gc_span_chunks(geo), ch0 = gc_span_first_chunk(geo, span) * 32;
-    int64_t p0, p1;
-    wgs_range(part, slab, &p0, &p1);
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const int frag = gc_wave_frag(geo, span, wave);  // (wave-uniform; -1: this wave multiplies rows of zeros and stores nothing)
-    int co_chunk = 0, ci_chunk = 0;
-    gc_frag_chunks(geo, frag < 0 ? 0 : frag, &co_chunk, &ci_chunk);
-    const int a_blk = frag < 0 ? wave : co_chunk - ch0 / 32, b_blk = frag < 0 ? wave : ci_chunk - ch0 / 32;
-    const int half = lane >> 5, wq = (lane >> 2) & 3;
-    const int cb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;  // byte offset of the lane's four channels in a row
-    const int a_base = L::DY + a_blk * CH * GC_ROW + cb, b_base = L::X + b_blk * L::XR * GC_ROW + cb, z_addr = L::ZERO + cb;
-
-    f32x16 acc[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[kx][e] = 0.f;
-
-    if (tid < GC_ROW / 16) *(u32x4 *) (smem + L::ZERO + tid * 16) = u32x4{0, 0, 0, 0};
-    const long x_shift = (long) (ky - 1) * W - 1;  // flat pixel offset of X row 0 of a chunk from the chunk's first pixel
-
-    for (int64_t c0 = p0; c0 < p1; c0 += CH) {
-        // ---- stage (16 bytes = 8 channels per item; per pixel NB blocks x 4 items); blocks behind C hold zeros
-        for (int i = tid; i < CH * 4 * NB; i += 256) {
-            const int t = i / (4 * NB), blk = (i % (4 * NB)) >> 2, q = i & 3;
-            const int64_t p = c0 + t;
-            const int ch = ch0 + blk * 32;
-            u32x4 v = {0, 0, 0, 0};
-            if (p < p1 && ch < C) v = *(const u32x4 *) (dz + p * C + ch + q * 8);
-            *(u32x4 *) (smem + L::DY + (blk * CH + t) * GC_ROW + q * 16) = v;
-        }
-        for (int i = tid; i < L::XR * 4 * NB; i += 256) {
-            const int u = i / (4 * NB), blk = (i % (4 * NB)) >> 2, q = i & 3;
-            const int64_t f = c0 + u + x_shift;
-            const int ch = ch0 + blk * 32;
-            u32x4 v = {0, 0, 0, 0};
-            if (f >= 0 && f < P && ch < C) v = *(const u32x4 *) (x + f * C + ch + q * 8);
-            *(u32x4 *) (smem + L::X + (blk * L::XR + u) * GC_ROW + q * 16) = v;
-        }
-        if (tid < CH) {
-            const int64_t p = c0 + tid;
-            int m = GC_NO_TAP;
-            if (p < p1) {  // (p <= 2^31 - 1: 32-bit division)
-                const unsigned row = (unsigned) p / (unsigned) W;
-                const int y = (int) (row % (unsigned) H) + ky - 1;
-                if (y >= 0 && y < H) m = (int) ((unsigned) p - row * (unsigned) W);
-            }
-            *(int *) (smem + L::META + tid * 4) = m;
-        }
-        __syncthreads();
-        // ---- multiply: all 64 lanes of all four waves (rows of zeros stand for what does not exist)
-        const int64_t left = p1 - c0;
-        const int steps = left >= CH ? CH / WGS_STEP : wgs_steps(left);
-        for (int s = 0; s < steps; ++s) {
-            const int t0 = WGS_STEP * s + 8 * half + wq, t1 = t0 + 4;
-            const s16x4 a0 = gc_read_tr(smem, a_base + t0 * GC_ROW);
-            const s16x4 a1 = gc_read_tr(smem, a_base + t1 * GC_ROW);
-            const bf16x8 A = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
-            const int m0 = *(const int *) (smem + L::META + t0 * 4), m1 = *(const int *) (smem + L::META + t1 * 4);
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const bool ok0 = (unsigned) (m0 + kx - 1) < (unsigned) W, ok1 = (unsigned) (m1 + kx - 1) < (unsigned) W;
-                const s16x4 b0 = gc_read_tr(smem, ok0 ? b_base + (t0 + kx) * GC_ROW : z_addr);
-                const s16x4 b1 = gc_read_tr(smem, ok1 ? b_base + (t1 + kx) * GC_ROW : z_addr);
-                const bf16x8 B = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
-                acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[kx], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
-    // ---- partial sums: D[i = co][j = ci], lane -> j = lane % 32, register e -> i = 8 * (e / 4) + 4 * (lane / 32) + e % 4
-    if (frag >= 0) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            float *out = ws + (((int64_t) slab * GCV_TAPS + ky * 3 + kx) * geo.frags + frag) * 1024 + (lane & 31);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) out[(8 * (e >> 2) + 4 * half + (e & 3)) * 32] = acc[kx][e];
-        }
-    }
-}
 
 // workspace [slab][tap][fragment][32][32] -> dw [co][cl][tap]
 __global__ __launch_bounds__(256) void gc_wgrad_reduce_kernel(const float *__restrict__ ws, int slabs, GcGeo geo, void *dw,
@@ -231,10 +152,7 @@ int gc_check(const char *who, int N, int Hin, int Win, int C, int cig, int strid
     c.Wout = gc_out_size(Win, stride);
     c.part = wgs_partition((int64_t) N * Hin, Win, slab_rows, gc_slabs_wanted(geo));
     c.bpart = wgs_partition((int64_t) N * c.Hout, c.Wout, slab_rows, gc_slabs_wanted(geo));
-    if (wgs_chain(c.part) > 0x7fffffffll || wgs_bias_chain(c.bpart) > 0x7fffffffll) {
-        snprintf(msg, sizeof msg, "%s: more than 2^31 - 1 steps in a chain (raise slab_rows)", who);
-        return cpn::fail(CPN_E_UNSUPPORTED, msg);
-    }
+    if (const int rc = ct_check_chains(who, c.part, c.bpart)) return rc;
     if (call) *call = c;
     return 0;
 }
@@ -298,11 +216,7 @@ int cpn_grouped_conv_wgrad_info(int32_t N, int32_t Hin, int32_t Win, int32_t C, 
     GcCall c;
     if (const int rc = gc_check("cpn_grouped_conv_wgrad_info", N, Hin, Win, C, cig, stride, slab_rows, &c)) return rc;
     if (!info) return cpn::fail(CPN_E_INVALID, "cpn_grouped_conv_wgrad_info: null pointer");
-    info[0] = c.part.slabs;
-    info[1] = c.part.slab_rows;
-    info[2] = c.part.steps;
-    info[3] = c.part.slabs;  // the reduce chain: one add per slab
-    info[4] = (int32_t) wgs_bias_chain(c.bpart);
+    wgs_info(c.part, c.bpart, info);
     return 0;
 }
 
@@ -322,8 +236,9 @@ int cpn_grouped_conv_wgrad(const void *x, const void *dz, const void *dy, int32_
     hipStream_t st = (hipStream_t) stream;
     float *ws = (float *) workspace, *wsb = ws + (int64_t) c.part.slabs * GCV_TAPS * c.geo.frags * 1024;
     if (dw) {
-        hipLaunchKernelGGL(gc_wgrad_slab_kernel, dim3((unsigned) c.part.slabs, (unsigned) c.geo.spans, 3u), dim3(256), 0, st,
-                           (const uint16_t *) dz, (const uint16_t *) x, ws, c.part, c.geo, Hin, (long) (c.part.rows * c.part.W));
+        hipLaunchKernelGGL((ct_wgrad_slab_kernel<3, 1, CtDense, GcSpans>), dim3((unsigned) c.part.slabs, (unsigned) c.geo.spans, 3u),
+                           dim3(256), 0, st, (const uint16_t *) dz, CtDense{(const uint16_t *) x, C}, ws, c.part, Hin, C,
+                           (long) (c.part.rows * c.part.W), GcSpans{c.geo});
         const long total = (long) C * cig * GCV_TAPS;
         hipLaunchKernelGGL(gc_wgrad_reduce_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, ws, c.part.slabs, c.geo, dw,
                            dw_dtype);

@@ -4,7 +4,7 @@
 // x is [N][HW][Cin] bf16 as it lies (a channels-last tensor), y and dy are [N][Cout][HW] planes, keep is [N][Cin] bytes.  The dropout
 // never touches x: the WEIGHT operand is masked per image (a dropped channel contributes an exact zero), the factor s = 1 / (1 - p)
 // is applied to the fp32 sum.  All three products run on v_mfma_f32_32x32x16_bf16 (D[i][j] = sum_k A[i][k] B[k][j]; lane l holds
-// A[l % 32][8 (l / 32) + e] and B[8 (l / 32) + e][l % 32], e = 0 ... 7; D: j = l % 32, i = 8 (reg / 4) + 4 (l / 32) + reg % 4):
+// A[l % 32][8 (l / 32) + e] and B[8 (l / 32) + e][l % 32], e = 0 ... 7; D: j = l % 32, i = mf_row(reg, l / 32); csrc/mfma_frag.h):
 //   rt_forward_kernel:   D[o][pixel] = W[o][c] x^T[c][pixel].  The pixel is on the lanes: a lane's B operand is 16 bytes of x as they
 //                        lie, every accumulator register is one output channel of 32 consecutive pixels (a coalesced store into an
 //                        NCHW plane).  The masked W of the workgroup's image sits in LDS as [step][lane half][o] x 16 bytes (64 B x
@@ -36,14 +36,10 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "mfma_frag.h"
 #include "tail_slabs.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int RT_F32 = 0, RT_BF16 = 1;
 constexpr int RT_ROW = 64;        // bytes of a staged x row: 32 channels
@@ -70,11 +66,6 @@ __device__ __forceinline__ u32x4 rt_pack8(const uint16_t e[8]) {
     return u32x4{(uint32_t) e[0] | ((uint32_t) e[1] << 16), (uint32_t) e[2] | ((uint32_t) e[3] << 16),
                  (uint32_t) e[4] | ((uint32_t) e[5] << 16), (uint32_t) e[6] | ((uint32_t) e[7] << 16)};
 }
-__device__ __forceinline__ s16x4 rt_read_tr(const char *smem, int byte_offset) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *) (smem + byte_offset));
-}
-// output channel of accumulator register reg in lane half h
-__device__ __forceinline__ int rt_row(int reg, int h) { return 8 * (reg >> 2) + 4 * h + (reg & 3); }
 
 __global__ __launch_bounds__(256) void rt_forward_kernel(const uint16_t *__restrict__ x, const void *__restrict__ w, int w_dtype,
                                                           const void *__restrict__ bias, int bias_dtype,
@@ -104,7 +95,7 @@ __global__ __launch_bounds__(256) void rt_forward_kernel(const uint16_t *__restr
     float b[16];
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int o = rt_row(reg, h);
+        const int o = mf_row(reg, h);
         b[reg] = bias && o < Cout ? rt_load_f32(bias, bias_dtype, o) : 0.f;
     }
     const int steps = Cin / 16;
@@ -114,8 +105,7 @@ __global__ __launch_bounds__(256) void rt_forward_kernel(const uint16_t *__restr
         const uint16_t *xp = x + ((int64_t) n * HW + (ok ? q : HW - 1)) * Cin + 8 * h;
         const char *ap = smem + (h * 32 + r) * 16;
         f32x16 acc;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) acc[reg] = 0.f;
+        mf_zero(acc);
         for (int st = 0; st < steps; st += 2) {  // (Cin is a multiple of 32: two steps per round, in ascending channel order)
             const bf16x8 B0 = *(const bf16x8 *) (xp + 16 * st), B1 = *(const bf16x8 *) (xp + 16 * st + 16);
             const bf16x8 A0 = *(const bf16x8 *) (ap + st * 1024), A1 = *(const bf16x8 *) (ap + st * 1024 + 1024);
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void rt_forward_kernel(const uint16_t *__restr
         if (ok) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int o = rt_row(reg, h);
+                const int o = mf_row(reg, h);
                 if (o < Cout) {
                     const float v = fmaf(acc[reg], s, b[reg]);
                     const int64_t at = ((int64_t) n * Cout + o) * HW + q;
@@ -163,7 +153,7 @@ __global__ __launch_bounds__(256) void rt_backward_kernel(const uint16_t *__rest
     tls_range(part, slab, &n, &q0, &q1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int r = lane & 31, h = lane >> 5, wq = (lane >> 2) & 3;
-    const int cb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;  // byte offset of the lane's four columns in a transposed read
+    const int cb = mf_lane_bytes(lane);
 
     if (dx) {  // item i = ((tile * ks + step) * 2 + lane half) * 32 + row: W[16 step + 8 half + j][channel of the row], j = 0 ... 7
         for (int i = tid; i < Cin * 2 * ks; i += 256) {
@@ -184,9 +174,7 @@ __global__ __launch_bounds__(256) void rt_backward_kernel(const uint16_t *__rest
 
     f32x16 acc[CT];
 #pragma unroll
-    for (int m = 0; m < CT; ++m)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) acc[m][reg] = 0.f;
+    for (int m = 0; m < CT; ++m) mf_zero(acc[m]);
     float bsum = 0.f;
     const int bo = tid & 31, bchain = tid >> 5;
 
@@ -218,15 +206,13 @@ __global__ __launch_bounds__(256) void rt_backward_kernel(const uint16_t *__rest
                 const int ct = t / (PT / 32), pt = t % (PT / 32);
                 if (pt >= ptiles) continue;  // (wave-uniform)
                 f32x16 d;
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) d[reg] = 0.f;
+                mf_zero(d);
 #pragma unroll
                 for (int st = 0; st < 2; ++st) {
                     if (st < ks) {
                         const bf16x8 A = *(const bf16x8 *) (WT + (((ct * ks + st) * 2 + h) * 32 + r) * 16);
                         const int g_at = (int) (GS - smem) + (16 * st + 8 * h + wq) * L::GS_ROW + pt * 64 + cb;
-                        const s16x4 b0 = rt_read_tr(smem, g_at), b1 = rt_read_tr(smem, g_at + 4 * L::GS_ROW);
-                        const bf16x8 B = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+                        const bf16x8 B = mf_operand(smem, g_at, g_at + 4 * L::GS_ROW);
                         d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, d, 0, 0, 0);
                     }
                 }
@@ -251,8 +237,7 @@ __global__ __launch_bounds__(256) void rt_backward_kernel(const uint16_t *__rest
                     const int ct = wave + 4 * m;
                     if (ct < ctiles) {  // (wave-uniform)
                         const int at = x_at + (ct * PT + 16 * st) * RT_ROW;
-                        const s16x4 b0 = rt_read_tr(smem, at), b1 = rt_read_tr(smem, at + 4 * RT_ROW);
-                        const bf16x8 B = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+                        const bf16x8 B = mf_operand(smem, at, at + 4 * RT_ROW);
                         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[m], 0, 0, 0);
                     }
                 }
@@ -268,7 +253,7 @@ __global__ __launch_bounds__(256) void rt_backward_kernel(const uint16_t *__rest
             if (ct < ctiles) {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
-                    const int o = rt_row(reg, h);
+                    const int o = mf_row(reg, h);
                     if (o < Cout) ws[((int64_t) slab * Cout + o) * Cin + ct * 32 + r] = acc[m][reg];
                 }
             }

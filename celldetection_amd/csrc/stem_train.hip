@@ -4,9 +4,9 @@
 // (kx 0..7, c 0..3) that output pixel (oy, ox) meets in filter row ky are the 64 contiguous bytes at Xp[n][2 oy + ky][2 ox].
 //
 //   st_pack_kernel:        weight [Cout][C][7][7] (fp32 | bf16) -> [7][Cout][32] bf16, zeros at kx = 7 and c >= C.
-//   st_forward_kernel:     the MFMA loop of stem7_kernel (csrc/stem.hip; restated here, that file is not touched): 14
-//                          v_mfma_f32_32x32x16_bf16 steps per 32-pixel fragment, operands straight from global memory, + bias,
-//                          no ReLU, 16-byte stores.
+//   st_forward_kernel:     the MFMA loop of stem7_kernel (csrc/stem_mfma.h, one text for both): 14 v_mfma_f32_32x32x16_bf16 steps
+//                          per 32-pixel fragment, operands straight from global memory, + bias, with this unit's epilogue: no
+//                          ReLU, bf16 by ct_bf16_rne, 16-byte stores.
 //   st_wgrad_slab_kernel:  dW_ky[Cout][32] = dY^T R_ky per filter row, the flat output pixel as the reduction index, 16 pixels per
 //                          MFMA step.  A workgroup owns a slab of output rows (csrc/wgrad_slabs.h) and all seven filter rows: per
 //                          chunk of 128 pixels the dY rows are staged in LDS once, wave w stages the 64-byte X rows of filter row
@@ -25,20 +25,15 @@
 
 #include "../../include/cpn_hip.h"
 #include "cpn_error.h"
+#include "mfma_frag.h"
 #include "pool_adjoint.h"
+#include "stem_mfma.h"
 #include "wgrad_bias.h"  // ct_bias_slab_kernel / ct_bias_reduce_kernel, ct_bf16_rne, the dtype codes
 #include "wgrad_slabs.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef u32x4 __attribute__((aligned(8))) u32x4_a8;  // a row of the padded input starts at a multiple of 8 bytes (odd W)
-typedef bf16x8 __attribute__((aligned(8))) bf16x8_a8;
 
 constexpr int ST_PAD_ROWS = 6, ST_PAD_COLS = 8;  // STEM_PAD_ROWS / STEM_PAD_COLS of csrc/cpn_kernels.h
 constexpr int ST_CH = 128;   // pixels per staged chunk (8 MFMA steps)
@@ -59,89 +54,30 @@ __global__ __launch_bounds__(256) void st_pack_kernel(const void *__restrict__ w
     out[e] = r;
 }
 
-// ---- forward: the loop of stem7_kernel without the ReLU -----------------------------------------------------------------------
+// ---- forward: stem_mfma_loop with an epilogue that has no activation -----------------------------------------------------------
 __device__ __forceinline__ unsigned int st_pack2(float lo, float hi) {
     return (unsigned int) ct_bf16_rne(lo) | ((unsigned int) ct_bf16_rne(hi) << 16);
 }
+
+struct StBf16 {
+    unsigned char *dst;
+    size_t stride;  // bytes per output pixel
+    __device__ __forceinline__ void operator()(const float (&v0)[4], const float (&v1)[4], int ch, size_t pixel, bool ok) const {
+        stem_store_bf16(dst + pixel * stride + (size_t) ch * 2, ok, st_pack2(v0[0], v0[1]), st_pack2(v0[2], v0[3]), st_pack2(v1[0], v1[1]),
+                        st_pack2(v1[2], v1[3]));
+    }
+};
 
 template <int NF>
 __global__ __launch_bounds__(256, 2) void st_forward_kernel(const unsigned char *__restrict__ xp, const unsigned char *__restrict__ wts,
                                                             const float *__restrict__ bias_p, unsigned char *__restrict__ dst, int N,
                                                             int H, int W, int Hout, int Wout) {
-    const int lane = threadIdx.x & 63;
-    const int l31 = lane & 31, lhi = lane >> 5;
     const int wave = (int) ((blockIdx.x * (unsigned) blockDim.x + threadIdx.x) >> 6);
     const int nwaves = (int) ((gridDim.x * (unsigned) blockDim.x) >> 6);
-    const int Wp = W + ST_PAD_COLS, Hp = H + ST_PAD_ROWS;
-    const int fx = (Wout + 31) >> 5;
-    const long nfrag = (long) N * Hout * fx;
-    constexpr int coutp = NF * 32;
-
-    bf16x8 wf[NF][14];
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-        for (int ks = 0; ks < 14; ++ks)
-            wf[j][ks] = *(const bf16x8 *) (wts + ((size_t) ((ks >> 1) * coutp + j * 32 + l31) * 32 + (ks & 1) * 16 + lhi * 8) * 2);
-    float bias[NF][4][4];
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bias[j][q][e] = bias_p ? bias_p[j * 32 + 8 * q + 4 * lhi + e] : 0.f;
-
-    for (long f = wave; f < nfrag; f += nwaves) {
-        const int tx = (int) (f % fx);
-        const long r = f / fx;
-        const int oy = (int) (r % Hout);
-        const int n = (int) (r / Hout);
-        const int ox = tx * 32 + l31;
-        const int oxc = ox < Wout ? ox : Wout - 1;  // lanes past the row end recompute its last pixel (never stored)
-        const unsigned char *p = xp + (((size_t) n * Hp + 2 * oy) * Wp + 2 * oxc) * 8 + lhi * 16;
-        bf16x8 bx[14];
-#pragma unroll
-        for (int ks = 0; ks < 14; ++ks) bx[ks] = *(const bf16x8_a8 *) (p + (size_t) (ks >> 1) * Wp * 8 + (ks & 1) * 32);
-        f32x16 acc[NF];
-#pragma unroll
-        for (int j = 0; j < NF; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 14; ++ks)
-#pragma unroll
-            for (int j = 0; j < NF; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][ks], bx[ks], acc[j], 0, 0, 0);
-        // lane (l31, lhi) holds channels j * 32 + 8 q + 4 lhi + e of pixel l31; one v_permlane32_swap pairs the two lane halves so
-        // that every lane owns 8 consecutive channels: 16-byte stores
-        unsigned char *drow = dst + (((size_t) n * Hout + oy) * Wout + ox) * (size_t) coutp * 2;
-#pragma unroll
-        for (int j = 0; j < NF; ++j)
-#pragma unroll
-            for (int qp = 0; qp < 2; ++qp) {
-                const int q0 = 2 * qp, q1 = q0 + 1;
-                float v0[4], v1[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v0[e] = acc[j][q0 * 4 + e] + bias[j][q0][e];
-                    v1[e] = acc[j][q1 * 4 + e] + bias[j][q1][e];
-                }
-                const int ch = j * 32 + 8 * (lhi ? q1 : q0);
-                const unsigned a0 = st_pack2(v0[0], v0[1]), a1 = st_pack2(v0[2], v0[3]);
-                const unsigned b0 = st_pack2(v1[0], v1[1]), b1 = st_pack2(v1[2], v1[3]);
-                const u32x2 s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                const u32x2 s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                u32x4 o;
-                o.x = s0.x; o.y = s1.x; o.z = s0.y; o.w = s1.y;
-                if (ox < Wout) *(u32x4 *) (drow + (size_t) ch * 2) = o;
-            }
-    }
+    stem_mfma_loop<NF>(xp, wts, bias_p, N, H + ST_PAD_ROWS, W + ST_PAD_COLS, Hout, Wout, wave, nwaves, StBf16{dst, (size_t) NF * 32 * 2});
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ s16x4 st_read_tr(const char *smem, int byte_offset) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *) (smem + byte_offset));
-}
-
 // LDS image: dY [NF blocks][ST_CH rows], X [4 waves][ST_CH rows]; rows of ST_ROW bytes, every offset a multiple of 16
 template <int NF>
 __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__restrict__ dy, const unsigned char *__restrict__ xp,
@@ -150,7 +86,7 @@ __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__re
     __shared__ __attribute__((aligned(16))) char smem[TOTAL];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int half = lane >> 5, wq = (lane >> 2) & 3;
-    const int cb = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;  // byte offset of the lane's four columns in a row
+    const int cb = mf_lane_bytes(lane);
     const int a_base = DY + cb, b_base = X + wave * ST_CH * ST_ROW + cb;
     const unsigned Wout = (unsigned) part.W;
     const int Wp = W + ST_PAD_COLS, Hp = H + ST_PAD_ROWS;
@@ -162,9 +98,7 @@ __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__re
 #pragma unroll
     for (int g = 0; g < 2; ++g)
 #pragma unroll
-        for (int m = 0; m < NF; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[g][m][r] = 0.f;
+        for (int m = 0; m < NF; ++m) mf_zero(acc[g][m]);
 
     for (int64_t c0 = p0; c0 < p1; c0 += ST_CH) {
         // ---- stage dY: 16 bytes = 8 channels per item, 4 NF items per pixel; zeros behind the slab's end
@@ -215,14 +149,10 @@ __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__re
             if (ky < 7) {
                 for (int s = 0; s < steps; ++s) {
                     const int t0 = WGS_STEP * s + 8 * half + wq, t1 = t0 + 4;
-                    const s16x4 b0 = st_read_tr(smem, b_base + t0 * ST_ROW);
-                    const s16x4 b1 = st_read_tr(smem, b_base + t1 * ST_ROW);
-                    const bf16x8 B = __builtin_bit_cast(bf16x8, __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7));
+                    const bf16x8 B = mf_operand(smem, b_base + t0 * ST_ROW, b_base + t1 * ST_ROW);
 #pragma unroll
                     for (int m = 0; m < NF; ++m) {
-                        const s16x4 a0 = st_read_tr(smem, a_base + (m * ST_CH + t0) * ST_ROW);
-                        const s16x4 a1 = st_read_tr(smem, a_base + (m * ST_CH + t1) * ST_ROW);
-                        const bf16x8 A = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
+                        const bf16x8 A = mf_operand(smem, a_base + (m * ST_CH + t0) * ST_ROW, a_base + (m * ST_CH + t1) * ST_ROW);
                         acc[g][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, acc[g][m], 0, 0, 0);
                     }
                 }
@@ -230,7 +160,7 @@ __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__re
             __syncthreads();
         }
     }
-    // ---- partial sums: D[i = co][j = (kx, c)], lane -> j = lane % 32, register r -> i = 8 * (r / 4) + 4 * (lane / 32) + r % 4
+    // ---- partial sums: D[i = co][j = (kx, c)], lane -> j = lane % 32, register r -> i = mf_row(r, lane / 32)
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const int ky = 4 * g + wave;
@@ -239,7 +169,7 @@ __global__ __launch_bounds__(256) void st_wgrad_slab_kernel(const uint16_t *__re
 #pragma unroll
             for (int m = 0; m < NF; ++m)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) out[(m * 32 + 8 * (r >> 2) + 4 * half + (r & 3)) * 32 + (lane & 31)] = acc[g][m][r];
+                for (int r = 0; r < 16; ++r) out[(m * 32 + mf_row(r, half)) * 32 + (lane & 31)] = acc[g][m][r];
         }
     }
 }

@@ -67,11 +67,13 @@ WGS_HD int64_t wgs_bias_chain(const WgSlabs &s) {
 }
 
 // the five numbers of a *_wgrad_info call: slabs, rows per slab, MFMA steps of the largest slab, and the two chains that the slabs
-// add to it -- the reduce chain (one add per slab) and the bias chain
-WGS_HD void wgs_info(const WgSlabs &s, int32_t info[5]) {
+// add to it -- the reduce chain (one add per slab) and the bias chain, of the bias gradient's own partition where a strided conv
+// gives dY other rows than x
+WGS_HD void wgs_info(const WgSlabs &s, const WgSlabs &bias, int32_t info[5]) {
     info[0] = s.slabs;
     info[1] = s.slab_rows;
     info[2] = s.steps;
     info[3] = s.slabs;
-    info[4] = (int32_t) wgs_bias_chain(s);
+    info[4] = (int32_t) wgs_bias_chain(bias);
 }
+WGS_HD void wgs_info(const WgSlabs &s, int32_t info[5]) { wgs_info(s, s, info); }

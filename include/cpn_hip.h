@@ -976,8 +976,8 @@ int cpn_components_label(const int32_t *in, int64_t pixel_stride, int64_t channe
 
 /* ---- Trainable convolution ---------------------------------------------------------------------------------
  * What celldetection_amd.nn.conv2d needs besides cpn_conv2d to train a dense stride-1 convolution (csrc/conv_train.hip,
- * csrc/wgrad_dense.h -- the one weight-gradient kernel of this section, of "Trainable concat convolution" and of "Trainable bilinear
- * resize" --, csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
+ * csrc/wgrad_dense.h -- the one weight-gradient kernel of this section, of "Trainable grouped convolution", of "Trainable concat
+ * convolution" and of "Trainable bilinear resize" --, csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
  *
  * The rule.  Supported: groups 1, stride 1, dilation 1, a square odd kernel k in {1, 3, 5, 7}, zero padding k / 2, cin and cout
  * positive multiples of 32.  Activations and weights are rounded to bf16 (round to nearest even), products accumulate in fp32,
@@ -1143,7 +1143,8 @@ int cpn_tail_backward(const void *x, const void *dy, int32_t dy_dtype, const voi
 
 /* ---- Trainable grouped convolution --------------------------------------------------------------------------
  * What celldetection_amd.nn.grouped_conv2d needs besides cpn_conv2d to train the 3x3 conv2 of a ResNeXt bottleneck block
- * (csrc/grouped_conv_train.hip, csrc/grouped_conv.h, csrc/wgrad_slabs.h).  Additions to ABI 22.  This text is the contract.
+ * (csrc/grouped_conv_train.hip, csrc/grouped_conv.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h; the weight gradient's slab kernel is
+ * the dense one's, csrc/wgrad_dense.h with csrc/mfma_frag.h).  Additions to ABI 22.  This text is the contract.
  *
  * The rule.  A conv of C -> C channels in groups of cig = C / groups channels, cig in {4, 8, 16, 32, 64}, kernel 3x3, zero padding
  * 1, dilation 1, stride 1 or 2.  It runs as bundles = C / bw block-diagonal dense convs of bw -> bw channels: bw = 32 for
@@ -1311,8 +1312,8 @@ int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, v
 /* ---- Trainable stem and max-pool ----------------------------------------------------------------------------
  * What celldetection_amd.nn.stem_conv2d and nn.max_pool2d run: the first two modules of a ResNet / ResNeXt encoder,
  * Conv2d(C <= 4 -> 32 | 64, 7x7, stride 2, padding 3) and MaxPool2d(3, 2, 1), and the MaxPool2d(2, 2) of the U-Net encoders
- * (csrc/stem_train.hip, csrc/pool_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the
- * contract.
+ * (csrc/stem_train.hip, csrc/stem_mfma.h -- the forward loop, shared with csrc/stem.hip --, csrc/mfma_frag.h, csrc/pool_adjoint.h,
+ * csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
  *
  * The stem's input is the padded 4-channel tensor Xp, bf16 [N][H + 6][W + 8][4] with a zero border (3 rows / columns in front) and
  * zeros in the channels c >= C, as cpn_convert_input_stem writes it (range_flag = NULL: a training input need not lie in [0, 1]).
@@ -1326,7 +1327,7 @@ int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, v
  *
  *   cpn_stem_train_forward: y[n][oy][ox][co] = sum over (ky, kx, c) of Xp[n][2 oy + ky][2 ox + kx][c] * packed[ky][co][kx][c]
  *   (+ bias[co], fp32, may be NULL), bf16 NHWC [N][Hout][Wout][cout], no activation.  The loop of the inference stem
- *   (csrc/stem.hip): 14 v_mfma_f32_32x32x16_bf16 steps per output in one fp32 accumulator, + 2 for the MFMA-internal sum, + the
+ *   (csrc/stem_mfma.h): 14 v_mfma_f32_32x32x16_bf16 steps per output in one fp32 accumulator, + 2 for the MFMA-internal sum, + the
  *   bias add, one rounding to bf16.
  *
  *   cpn_stem_wgrad: dw[co][c][ky][kx] = sum over (n, oy, ox) of dY[n][oy][ox][co] * Xp[n][2 oy + ky][2 ox + kx][c] for kx < 7 and

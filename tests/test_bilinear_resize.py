@@ -293,9 +293,11 @@ def test_header_binding_and_exports_agree():
     src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'bilinear_train.hip')).read()
     dense = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'wgrad_dense.h')).read()  # the slab kernel, compiled inside the unit
     assert '#include "wgrad_dense.h"' in src and 'wgrad_dense.h' in build.HEADERS
-    for text in (src, dense):
+    frag = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'mfma_frag.h')).read()  # the fragment idiom, included by the header
+    assert '#include "mfma_frag.h"' in dense and 'mfma_frag.h' in build.HEADERS
+    for text in (src, dense, frag):
         assert 'atomic' not in text.replace('No floating-point atomics', '') and 'fmaf' not in text and 'fma(' not in text
-    assert 'ds_read_tr16_b64' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'ba_tap' in src and 'ba_first' in src
+    assert 'ds_read_tr16_b64' in frag and 'mf_operand(' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'ba_tap' in src and 'ba_first' in src
     adj = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'bilinear_adjoint.h')).read()
     assert 'fmaxf(scale * ((float) dst + 0.5f) - 0.5f, 0.f)' in adj and '*i0 + (*i0 < in_size - 1)' in adj
     assert 'fmaxf(fmaf(scale, (float) dst + 0.5f, -0.5f), 0.f)' in adj

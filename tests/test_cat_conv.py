@@ -251,7 +251,9 @@ def test_header_binding_and_exports_agree():
     assert '#include "wgrad_dense.h"' in src and 'wgrad_dense.h' in build.HEADERS
     for text in (src, dense):
         assert 'conv_igemm_kernel' not in text and 'atomic' not in text.replace('No floating-point atomics', '')
-    assert 'ds_read_tr16_b64' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'na_pixel_src' in src
+    frag = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'mfma_frag.h')).read()  # the fragment idiom, included by the header
+    assert '#include "mfma_frag.h"' in dense and 'mfma_frag.h' in build.HEADERS and 'atomic' not in frag
+    assert 'ds_read_tr16_b64' in frag and 'mf_operand(' in dense and 'mfma_f32_32x32x16_bf16' in dense and 'na_pixel_src' in src
     for doc in ('README.md', 'DESIGN.md', 'INTEGRATION.md'):
         assert 'cat_conv2d' in open(os.path.join(ROOT, doc)).read(), doc
 

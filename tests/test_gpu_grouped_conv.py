@@ -18,6 +18,7 @@ import torch
 import celldetection_amd as cda
 import conv_bounds as cb
 import grouped_conv_oracle as oracle
+from test_gpu_cat_conv import same_partition
 from test_gpu_conv_train import bf16_exact, check_sum, same_bits
 from test_grouped_conv import GPU_SHAPES, Bottleneck
 
@@ -194,6 +195,26 @@ def test_one_hot_operands_hit_exactly_the_predicted_element(c, cig, stride):
             assert torch.equal(dw.double().cpu(), want), (n0, y0, x0, slab_rows, dw.nonzero().tolist()[:8])
             assert torch.equal(db.cpu(), dy.sum((0, 2, 3)))
     assert hits >= 3, hits
+
+
+@pytest.mark.parametrize('slab_rows', [8, 1])
+@pytest.mark.parametrize('c', [32, 64])
+def test_grouped_route_at_one_group_is_the_dense_route_bit_for_bit(c, slab_rows):
+    """One group of 32 channels is one 32-wide bundle, one of 64 the four fragments of a 64-wide group: the diagonal fragments are then
+    the whole (co, ci) matrix, and both routes run the same slab kernel (csrc/wgrad_dense.h) under two tilings.  With the same slabs
+    both add the same 16-pixel steps in the same ascending order into one accumulator per element, and the reduce adds the same slabs
+    in the same order.  N = 3, 5 x 33: at slab_rows 8 a slab has 264 pixels, which the dense grid cuts into chunks of 128, 128, 8 and the
+    grouped one into 64, 64, 64, 64, 8 -- the same partial last step, the second image starting inside a chunk in both; at 1 every slab
+    is one partial chunk of 33 pixels.  slab_rows 0 is left out: the two auto partitions ask for different numbers of slabs."""
+    n, h, w = 3, 5, 33
+    x, dy = bf16_exact(n, c, h, w, seed=800 + c).cuda(), bf16_exact(n, c, h, w, seed=900 + c).cuda()
+    info = same_partition(nn.grouped_weight_grad_info(n, h, w, c, 1, 1, slab_rows), nn.weight_grad_info(n, h, w, c, c, 3, slab_rows))
+    assert (info['slabs'], info['slab_rows'], info['steps']) == (-(-n * h // slab_rows), slab_rows, -(-slab_rows * w // 16)), info
+    assert bool(torch.isfinite(x).all() and torch.isfinite(dy).all())
+    dw, db = nn.grouped_conv2d_weight_grad(x, dy, 1, 1, slab_rows)
+    dw_dense, db_dense = nn.conv2d_weight_grad(x, dy, 3, slab_rows)
+    assert dw.shape == dw_dense.shape == (c, c, 3, 3) and bool((dw != 0).any())
+    assert same_bits(dw, dw_dense) and same_bits(db, db_dense), (c, slab_rows, info, (dw != dw_dense).nonzero()[:4].tolist())
 
 
 # ---- layout and gradient plumbing

@@ -242,7 +242,12 @@ def test_header_binding_and_exports_agree():
             'max_pool2d', 'MaxPool2d', 'convert_maxpool2d_'} <= set(nn.__all__)
     src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'stem_train.hip')).read()
     assert 'atomic' not in src.replace('No floating-point atomics', '') and 'fmaxf' not in src
-    assert 'ds_read_tr16_b64' in src and 'mfma_f32_32x32x16_bf16' in src and 'permlane32_swap' in src
+    # the forward loop and its swap-and-store are csrc/stem_mfma.h (shared with csrc/stem.hip), the transposed read csrc/mfma_frag.h
+    loop, frag = (open(os.path.join(ROOT, 'celldetection_amd', 'csrc', name)).read() for name in ('stem_mfma.h', 'mfma_frag.h'))
+    assert '#include "stem_mfma.h"' in src and '#include "mfma_frag.h"' in src and {'stem_mfma.h', 'mfma_frag.h'} <= set(build.HEADERS)
+    assert 'atomic' not in loop + frag and 'fmaxf' not in loop + frag
+    assert 'ds_read_tr16_b64' in frag and 'mf_operand(' in src and 'mfma_f32_32x32x16_bf16' in src
+    assert 'mfma_f32_32x32x16_bf16' in loop and 'permlane32_swap' in loop and 'stem_mfma_loop<NF>(' in src
     for doc in ('README.md', 'DESIGN.md', 'INTEGRATION.md'):
         text = open(os.path.join(ROOT, doc)).read()
         assert 'stem_conv2d' in text and 'max_pool2d' in text, doc

@@ -38,14 +38,17 @@ def test_library_accepts_exactly_the_tables_filter_sizes():
 def test_constants_are_the_headers():
     dense, slabs = _text('wgrad_dense.h'), _text('wgrad_slabs.h')
     assert int(re.search(r'constexpr int CT_CH = (\d+);', dense).group(1)) == tt.CT_CH == 128
+    assert 'static constexpr int CH = CT_CH, FR = MT, DYB = 2 * MT, XB = 2;' in dense  # ... which is the dense grid's chunk
     assert int(re.search(r'constexpr int WGS_STEP = (\d+);', slabs).group(1)) == tt.WGS_STEP == 16
     body = re.search(r'constexpr int ct_mt\(int k\) \{ return (.*?); \}', dense).group(1)
     assert body == 'k <= 3 ? 2 : 1', body
     assert [tt.mt(k) for k in (1, 3, 5, 7)] == [2, 2, 1, 1]
-    # the tile extents and the split of blockIdx.y the edges 'grid', 'co_part' and 'ci_part' speak of
-    assert 'co0 = (int) (blockIdx.y / tiles_ci) * 64 * MT, ci0 = (int) (blockIdx.y % tiles_ci) * 64;' in dense
+    # the tile extents and the split of blockIdx.y the edges 'grid', 'co_part' and 'ci_part' speak of: the dense Tiling (CtGrid)
+    assert 'co0 = (int) (by / tiles_ci) * 64 * MT, ci0 = (int) (by % tiles_ci) * 64;' in dense
+    assert 'tiling.tile(blockIdx.y, wave, lane)' in dense and 'class Tiling = CtGrid<MT>>' in dense
     assert 'return (cout + 64 * ct_mt(k) - 1) / (64 * ct_mt(k));' in dense and 'tci = (cin + 63) / 64;' in dense
-    assert 'const int steps = left >= CT_CH ? CT_CH / WGS_STEP : wgs_steps(left);' in dense
+    assert 'constexpr int PAD = K / 2, CH = Tiling::CH, FR = Tiling::FR;' in dense
+    assert 'const int steps = left >= CH ? CH / WGS_STEP : wgs_steps(left);' in dense
 
 
 @pytest.mark.parametrize('inst', INSTANTIATIONS)
