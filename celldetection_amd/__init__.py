@@ -6,7 +6,7 @@ loop.  Everything computes in hand-written HIP kernels behind the C ABI of ``lib
 (``include/cpn_hip.h``); there is no CPU fallback.
 """
 from . import cpn as models  # ``cd.models.CpnResNeXt101UNet`` -> ``celldetection_amd.models.CpnResNeXt101UNet``
-from . import (components, flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, nn, objective, ops, overlay, preprocess, region_props, shape_props, synth,
+from . import (components, flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, nn, objective, ops, optim, overlay, preprocess, region_props, shape_props, synth,
                targets, util)
 from .components import (fill_label_gaps_, label_components, masks2labels, relabel_, remove_partials_, rgb_to_scalar, stack_labels,
                          unary_masks2labels)
@@ -15,6 +15,7 @@ from .fourier import contours2fourier, efd, labels2fourier
 from .h5 import from_h5, to_h5
 from .instance_eval import LabelMatcher, LabelMatcherList
 from .objective import CPNObjective, collate_cpn_targets
+from .optim import AdamW, clip_grad_norm_, grad_norm, step_info
 from .region_props import labels2property_table, region_properties
 from .shape_props import shape_properties
 from .label_contours import labels2contour_list as labels2contours  # ``cd.data.labels2contours`` is that function
@@ -31,4 +32,5 @@ __all__ = ['models', 'ops', 'util', 'synth', 'inference', 'labels', 'contours2la
            'label_cmap', 'random_colors_hsv', 'label_contours', 'labels2contours', 'resample_contours', 'fourier', 'efd', 'contours2fourier',
            'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator',
            'objective', 'CPNObjective', 'collate_cpn_targets', 'components', 'label_components', 'relabel_', 'stack_labels',
-           'rgb_to_scalar', 'unary_masks2labels', 'masks2labels', 'fill_label_gaps_', 'remove_partials_', 'nn']
+           'rgb_to_scalar', 'unary_masks2labels', 'masks2labels', 'fill_label_gaps_', 'remove_partials_', 'nn',
+           'optim', 'AdamW', 'clip_grad_norm_', 'grad_norm', 'step_info']

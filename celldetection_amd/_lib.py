@@ -43,6 +43,8 @@ COMPONENTS_MODES = {'equal': COMPONENTS_EQUAL, 'nonzero': COMPONENTS_NONZERO}
 CONV_PACK_FORWARD, CONV_PACK_DGRAD = 0, 1
 CONV_PACK_MODES = {'forward': CONV_PACK_FORWARD, 'dgrad': CONV_PACK_DGRAD}
 CONV_TRAIN_F32, CONV_TRAIN_BF16 = 0, 1
+# optimizer step (CPN_OPTIM_* of include/cpn_hip.h)
+OPTIM_CHUNK, OPTIM_FLAG_SCALAR, OPTIM_TENSOR_BYTES = 8192, 1, 80
 
 
 class TensorDesc(Structure):
@@ -301,6 +303,13 @@ _SIGNATURES = [
                                              c_void_p, c_void_p]),
     ('cpn_maxpool2d_backward', ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                               c_int32, c_void_p, c_void_p]),
+    ('cpn_optim_info', ctypes.c_int, [POINTER(c_int64), c_int32, POINTER(c_int64), POINTER(c_int64)]),
+    ('cpn_optim_chunk_map', ctypes.c_int, [POINTER(c_int64), c_int32, c_void_p, c_int64]),
+    ('cpn_optim_upload', ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    ('cpn_optim_sumsq', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    ('cpn_optim_norm', ctypes.c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p]),
+    ('cpn_optim_adamw', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
+    ('cpn_optim_scale', ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
 ]
 
 EXPORTED_SYMBOLS = tuple(s[0] for s in _SIGNATURES)

@@ -68,6 +68,9 @@ SOURCES = {
     # trainable ResNet stem (7x7 stride-2 conv on the padded 4-channel input: pack, forward, weight gradient) and max-pool with its
     # tap index and gather gradient (index arithmetic: csrc/pool_adjoint.h)
     'stem_train.hip': [],
+    # the optimizer step (global gradient norm, clip, AdamW): fp64 sums in a fixed order and an fp32 update defined operation by
+    # operation (partition and lane mapping: csrc/optim_chunks.h): no FMA contraction, correctly rounded division and square root
+    'optim.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -76,7 +79,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'optim_chunks.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

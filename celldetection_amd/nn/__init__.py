@@ -19,7 +19,8 @@ is supported (with its known limits), in the order a step meets them:
   no stock operation between the image and the head maps.
 
 _common.py holds what the families share.  The rules are the "Trainable ..." sections of include/cpn_hip.h; ``cda.models.*`` stay
-inference-only.
+inference-only.  The step ends outside this package: ``cda.optim`` clips the gradients by their global norm and applies AdamW on the
+same library ("Optimizer step" of the header).
 """
 from .batch_norm import ACTIVATIONS, BatchNorm2d, batch_norm, batch_norm_forward, batch_norm_info
 from .blocks import Bottleneck, CPNCore, UNetDecoder

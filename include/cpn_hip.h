@@ -1456,6 +1456,88 @@ int cpn_resized_conv_wgrad(const void *x, const void *dy, int32_t N, int32_t H, 
 int cpn_bilinear_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, void *dst, int32_t h, int32_t w, void *stream);
 int cpn_bilinear_sum_f32(const float *t, int64_t planes, int32_t H, int32_t W, float *dst, int32_t h, int32_t w, void *stream);
 
+/* ---- Optimizer step -----------------------------------------------------------------------------------------
+ * What celldetection_amd.optim (AdamW, clip_grad_norm_, grad_norm, step_info) runs on: the global L2 norm of a list of gradients,
+ * the clip coefficient, the AdamW update and the in-place scaling of the gradients, each one multi-tensor launch
+ * (csrc/optim.hip, csrc/optim_chunks.h).  They stand for torch.nn.utils.clip_grad_norm_ followed by torch.optim.AdamW.step, which
+ * is what the reference trains with by default (models/lightning_base.py:397-400, dict(AdamW=dict()), under the trainer's gradient
+ * clip).  Additions to ABI 22.  This text is the contract.
+ *
+ * The list.  n tensors; tensor t has numel[t] >= 0 contiguous elements of dtype 0 (fp32) or 1 (bf16), the codes of "Trainable
+ * convolution".  Every tensor is cut on its own into chunks of CPN_OPTIM_CHUNK consecutive elements (the last one partial, a tensor
+ * of 0 elements has none), tensor after tensor: chunk c of the list is chunk map[c][1] of tensor map[c][0].  The map is int32 [chunks][2]
+ * and depends on the sizes alone.  One workgroup of 256 lanes takes one chunk at a time (at most 2048 workgroups, which walk more
+ * chunks with that stride).  In a chunk, 16 bytes of the tensor's dtype (4 fp32 or 8 bf16 elements) are an item; item q belongs to
+ * lane q % 256; a lane takes its items and the elements of an item in ascending order.  A lane moves a whole item with 16-byte
+ * loads and stores (the fp32 state of 8 bf16 elements: two each) and the partial last item of a tensor element by element.  A
+ * tensor one of whose addresses is not 16-byte aligned (CPN_OPTIM_FLAG_SCALAR, set by cpn_optim_upload) moves every item
+ * element by element: the same lanes, the same order, the same results.
+ *
+ * The table.  CpnOptimTensor[n] in device memory, 8-byte aligned, one record per tensor: the four addresses, the size, the dtype
+ * of p and g (m and v are fp32 whatever it is) and the fp32 scalars of the update, which the caller computes in fp64 and rounds
+ * once:
+ *     decay = 1 - lr * weight_decay,  w1 = 1 - beta1,  beta2,  w2 = 1 - beta2,  eps,  step_size = lr / (1 - beta1^t),
+ *     bc2_sqrt = sqrt(1 - beta2^t),   t = the step count of the tensor after this step (>= 1).
+ * (lr itself is carried for the record; the kernels do not read it.)  Steps and hyper-parameters may differ from tensor to tensor.
+ *   cpn_optim_upload: validates a host table (pinned memory, or the copy is not asynchronous), writes every record's flags
+ *   (CPN_OPTIM_FLAG_SCALAR where (p | g | m | v) & 15, opt_flags of csrc/optim_chunks.h; with_state = 0 clears p, m, v first: the
+ *   norm and the scaling read g alone) and enqueues ONE hipMemcpyAsync of n records to `device` on the stream.  The host table
+ *   must stay unchanged until that copy has run (the caller's ring of staging buffers).  CPN_E_INVALID: a negative size, an
+ *   unknown dtype, a null address of a non-empty tensor, an address not aligned to its element.  n = 0 does nothing.
+ *   cpn_optim_info: info[3] = {CPN_OPTIM_CHUNK, chunks, fp64 partials (= chunks)}; per_tensor (or NULL) int64 [n][3] =
+ *   {first chunk, chunks, elements of the last chunk (0 for an empty tensor)}.  cpn_optim_chunk_map fills a host map of
+ *   `chunks` records (CPN_E_INVALID where chunks is not the count of cpn_optim_info).  Host arithmetic: both answer without a GPU.
+ *   More than 2^31 - 1 chunks: CPN_E_UNSUPPORTED.
+ * A launch trusts no record of the map: one that names no tensor of the table, or a chunk past a tensor's end, is skipped, so
+ * a map that does not fit the table can leave elements out and cannot reach outside a tensor.  cpn_optim_adamw skips a record
+ * without p, m or v (a table uploaded with with_state = 0).
+ *
+ * The norm.  cpn_optim_sumsq writes one fp64 partial per chunk: a lane adds the squares of its elements, widened to fp64 (the
+ * product is exact), in the order above; the 64 lanes of a wave are added by halving (lane l += lane l + 32, 16, 8, 4, 2, 1); the
+ * four waves ((w0 + w1) + w2) + w3.  cpn_optim_norm (one workgroup): lane l adds partials [l * per, min(chunks, (l + 1) * per)),
+ * per = ceil(chunks / 256), in ascending order, then the 256 lane sums are added in ascending order: S.  It writes
+ *     norm_coef[0] = norm = (float) sqrt(S)                                   (fp64 square root, one rounding to fp32),
+ *     norm_coef[1] = coef = (float) min(1, max_norm / ((double) norm + 1e-6))  (fp64, one rounding),
+ * the clip_coef_clamped of torch.nn.utils.clip_grad_norm_; max_norm = +inf gives 1 (the norm alone), max_norm < 0 or NaN is
+ * CPN_E_INVALID.  chunks = 0: norm 0.  No floating-point atomics: bit-identical from run to run.  A non-finite gradient gives a
+ * non-finite norm, and a NaN coefficient stays NaN; nothing is skipped.
+ *
+ * The update.  cpn_optim_adamw, per element, every operation one fp32 operation rounded to nearest (no fma; IEEE division and
+ * square root), in the order of torch's single-tensor path (torch/optim/adam.py _single_tensor_adam with decoupled decay):
+ *     g = g * coef                        (coef = *coef, the word cpn_optim_norm wrote; coef == NULL: 1, and g * 1 is g)
+ *     p = p * decay
+ *     m = m + (g - m) * w1
+ *     v = v * beta2 + (g * g) * w2
+ *     denom = sqrt(v) / bc2_sqrt + eps
+ *     p = p - step_size * (m / denom)
+ * bf16 p and g widen exactly; the new p is rounded once to bf16 (to nearest even).  g is not written.  nontemporal = 1 stores m
+ * and v with the non-temporal hint (same results; profiles/optim.txt says which is faster).
+ * cpn_optim_scale: g = g * coef rounded once to g's dtype (for bf16 the product is formed exactly in fp64 first), in place: the
+ * gradient scaling of clip_grad_norm_.
+ * Every call validates before it reads a pointer; chunks = 0 launches nothing.
+ * Known limits: not captured into a hipGraph by the caller (the table is uploaded per step); no fp32 master copy of a bf16
+ * parameter; no skipping of a step on a non-finite norm; one workgroup per chunk, so a list of tiny tensors runs mostly idle lanes.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_OPTIM_CHUNK 8192
+#define CPN_OPTIM_FLAG_SCALAR 1
+typedef struct CpnOptimTensor {
+    void *p;         /* parameter, dtype below (unused by the norm and the scaling) */
+    void *g;         /* gradient, the same dtype */
+    float *m, *v;    /* exp_avg, exp_avg_sq */
+    int64_t numel;
+    int32_t dtype;   /* 0 fp32, 1 bf16 */
+    int32_t flags;   /* written by the upload */
+    float lr, decay, w1, beta2, w2, eps, step_size, bc2_sqrt;
+} CpnOptimTensor;    /* 80 bytes */
+int cpn_optim_info(const int64_t *numel, int32_t n, int64_t info[3], int64_t *per_tensor);
+int cpn_optim_chunk_map(const int64_t *numel, int32_t n, int32_t *map, int64_t chunks);
+int cpn_optim_upload(CpnOptimTensor *host, int32_t n, int32_t with_state, void *device, void *stream);
+int cpn_optim_sumsq(const void *table, int32_t n, const int32_t *map, int64_t chunks, double *partials, void *stream);
+int cpn_optim_norm(const double *partials, int64_t chunks, double max_norm, float *norm_coef, void *stream);
+int cpn_optim_adamw(const void *table, int32_t n, const int32_t *map, int64_t chunks, const float *coef, int32_t nontemporal,
+                    void *stream);
+int cpn_optim_scale(const void *table, int32_t n, const int32_t *map, int64_t chunks, const float *coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
