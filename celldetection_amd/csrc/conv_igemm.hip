@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "../../include/cpn_hip.h"
 #include "cpn_error.h"
 #include "cpn_kernels.h"
 #include "lds_dma.h"

@@ -28,7 +28,7 @@ from ._lib import check, ptr, stream_ptr
 __all__ = ['resolve_label_channels']
 
 CROSS = 0o272  # footprint bits, bit 3 * row + column: 010 / 111 / 010
-MAX_STEPS = 8  # CPN_FLAT_MAX_STEPS of include/cpn_hip.h: synchronous steps per launch
+MAX_STEPS = _lib.FLAT_MAX_STEPS  # synchronous steps per launch
 
 
 def _footprint(kernel):

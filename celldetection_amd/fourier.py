@@ -45,8 +45,7 @@ from .label_contours import labels2contours_packed
 
 __all__ = ['efd_packed', 'efd', 'contours2fourier', 'labels2fourier']
 
-CHUNK = 256  # CPN_EFD_CHUNK of include/cpn_hip.h
-MAX_ORDER = 64  # CPN_EFD_MAX_ORDER
+CHUNK, MAX_ORDER = _lib.EFD_CHUNK, _lib.EFD_MAX_ORDER
 POINTS_I32, POINTS_F64 = 0, 1  # CPN_EFD_POINTS_*
 CLOSE_NONE, CLOSE_ALL, CLOSE_EACH, TIMED = 0, 1, 2, 256  # CPN_EFD_CLOSE_*, CPN_EFD_TIMED
 STATUS_WORDS = 8

@@ -45,7 +45,7 @@ from ._lib import check, ptr, stream_ptr
 __all__ = ['labels2contours_packed', 'labels2contours', 'labels2contour_list', 'resample_contours_packed', 'resample_contours']
 
 RETR_EXTERNAL, CHAIN_APPROX_NONE = 0, 1  # cv2's enum values
-TILE = 32  # CPN_CONTOURS_TILE of include/cpn_hip.h
+TILE = _lib.CONTOURS_TILE
 
 
 def _check_mode(mode, method):

@@ -42,12 +42,18 @@ MAPS = 8  # chunk maps kept per device
 NONTEMPORAL = 0  # the store policy of m and v (profiles/optim.txt: the non-temporal hint measured against plain stores)
 _MOMENTS = ('exp_avg', 'exp_avg_sq')
 _UNSUPPORTED = ('amsgrad', 'maximize', 'capturable', 'differentiable', 'foreach', 'fused')
-# CpnOptimTensor of include/cpn_hip.h
-_RECORD = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('numel', '<i8'), ('dtype', '<i4'), ('flags', '<i4'),
-                    ('lr', '<f4'), ('decay', '<f4'), ('w1', '<f4'), ('beta2', '<f4'), ('w2', '<f4'), ('eps', '<f4'),
-                    ('step_size', '<f4'), ('bc2_sqrt', '<f4')])
+
+
+def _record_dtype(struct):
+    """The numpy dtype of a ctypes Structure: the same names, offsets and size, a pointer as its address ('<u8').  (np.dtype(struct)
+    itself refuses pointer fields.)"""
+    names = [name for name, _ in struct._fields_]
+    return np.dtype(dict(names=names, formats=['<u8' if t is ctypes.c_void_p else np.dtype(t).str for _, t in struct._fields_],
+                         offsets=[getattr(struct, name).offset for name in names], itemsize=ctypes.sizeof(struct)))
+
+
+_RECORD = _record_dtype(_lib.OptimTensor)  # CpnOptimTensor of include/cpn_hip.h
 _SCALARS = ('lr', 'decay', 'w1', 'beta2', 'w2', 'eps', 'step_size', 'bc2_sqrt')
-assert _RECORD.itemsize == _lib.OPTIM_TENSOR_BYTES
 
 
 def step_info(numels, dtypes=None):
@@ -124,8 +130,8 @@ class _Engine:
         return slot, slot[0].numpy().view(_RECORD)[:n]
 
     def upload(self, slot, n, with_state):
-        _lib.check(_lib.load().cpn_optim_upload(_lib.ptr(slot[0]), n, int(with_state), _lib.ptr(self.table), _lib.stream_ptr()),
-                   'optim_upload')
+        records = ctypes.cast(slot[0].data_ptr(), ctypes.POINTER(_lib.OptimTensor))
+        _lib.check(_lib.load().cpn_optim_upload(records, n, int(with_state), _lib.ptr(self.table), _lib.stream_ptr()), 'optim_upload')
         slot[1] = torch.cuda.Event()
         slot[1].record()
 

@@ -31,7 +31,7 @@ from ._lib import check, ptr, stream_ptr
 
 __all__ = ['contours2overlay', 'label_cmap', 'random_colors_hsv']
 
-TILE = 32  # CPN_OVERLAY_TILE of include/cpn_hip.h
+TILE = _lib.OVERLAY_TILE
 _SUM_BITS_LIMIT = (2 ** 32 - 1) // 255  # the kernel's sums are 32 bits wide
 QUALITATIVE_MAPS = ('Pastel1', 'Pastel2', 'Paired', 'Accent', 'Dark2', 'Set1', 'Set2', 'Set3', 'tab10', 'tab20', 'tab20b', 'tab20c')
 

@@ -47,8 +47,8 @@ from .label_contours import _split, labels2contours_packed, resample_contours_pa
 
 __all__ = ['labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator']
 
-DIST_L1, DIST_L2, DIST_C = 1, 2, 3  # CPN_DIST_* of include/cpn_hip.h = cv2's enum values
-MAX_STEPS = 8  # CPN_LABEL_DISTANCES_MAX_STEPS: synchronous steps per launch
+DIST_L1, DIST_L2, DIST_C = _lib.DIST_L1, _lib.DIST_L2, _lib.DIST_C  # = cv2's enum values
+MAX_STEPS = _lib.LABEL_DISTANCES_MAX_STEPS  # synchronous steps per launch
 MAX_SIDE = 32768
 
 

@@ -31,6 +31,8 @@ extern "C" {
 #define CPN_E_WORKSPACE (-3)
 #define CPN_E_INTERNAL (-4) /* a bound that holds by construction was reached (ABI 20: the contour trace) */
 
+#define CPN_HOST /* the pointer is to host memory; an array parameter (`int32_t info[5]`) always is and carries no mark */
+
 const char *cpn_last_error(void);
 int cpn_abi_version(void);
 
@@ -195,13 +197,13 @@ void cpn_plan_destroy(cpn_plan *plan);
 int64_t cpn_plan_workspace_bytes(cpn_plan *plan, int32_t N, int32_t H, int32_t W);
 /* Spatial size (h, w) of the external output CPN_OUT_* for an H x W input (0 x 0: the plan has no such output), and
  * the element count per image of the largest activation tensor (callers split batches at 2^31 elements). */
-int cpn_plan_output_dims(cpn_plan *plan, int32_t H, int32_t W, int32_t out_index, int32_t *h, int32_t *w);
+int cpn_plan_output_dims(cpn_plan *plan, int32_t H, int32_t W, int32_t out_index, CPN_HOST int32_t *h, CPN_HOST int32_t *w);
 int64_t cpn_plan_max_tensor_elements(cpn_plan *plan, int32_t H, int32_t W);
 /* Location of activation tensor `tensor` inside the workspace of a (N, H, W) run: byte offset, spatial size and channel
  * stride (padded channel count; NHWC, bf16 / e4m3 / fp32 by plan precision).  Only tensors that are live at the end of the
  * run may be read afterwards -- the sources of CPN_OP_CONV_DEFERRED ops are. */
-int cpn_plan_tensor_info(cpn_plan *plan, int32_t N, int32_t H, int32_t W, int32_t tensor, int64_t *byte_offset,
-                         int32_t *h, int32_t *w, int32_t *channel_stride);
+int cpn_plan_tensor_info(cpn_plan *plan, int32_t N, int32_t H, int32_t W, int32_t tensor, CPN_HOST int64_t *byte_offset,
+                         CPN_HOST int32_t *h, CPN_HOST int32_t *w, CPN_HOST int32_t *channel_stride);
 /* 2*MAC FLOPs executed by the MFMA loops for that shape (includes channel/tile padding). */
 double cpn_plan_executed_flops(cpn_plan *plan, int32_t N, int32_t H, int32_t W);
 
@@ -226,7 +228,7 @@ int cpn_plan_run_stats(cpn_plan *plan, const void *input, int32_t in_dtype, int3
 int cpn_plan_num_ops(cpn_plan *plan);
 int cpn_plan_run_timed(cpn_plan *plan, const void *input, int32_t in_dtype, int32_t N, int32_t H, int32_t W,
                        void *workspace, int64_t workspace_bytes, float *const *outputs, int32_t *range_flag,
-                       void *stream, float *op_ms, double *op_flops);
+                       void *stream, CPN_HOST float *op_ms, CPN_HOST double *op_flops);
 
 /* Single convolution (testing / building blocks); same semantics as one CPN_OP_CONV. */
 int cpn_conv2d(const cpn_op_desc *op, const void *src0, int32_t c0_stride, const void *src1, int32_t c1_stride,
@@ -376,7 +378,7 @@ int cpn_gather_channels(const float *map, const int32_t *indices, int64_t P, int
  * (int32 [nseg], device) receives the number kept per segment.
  * ---------------------------------------------------------------------------------------------------------- */
 int64_t cpn_nms_workspace_bytes(int64_t P, int64_t max_segment, int32_t nseg);
-int cpn_nms(const float *boxes, const float *scores, int64_t P, const int64_t *seg_offsets_host,
+int cpn_nms(const float *boxes, const float *scores, int64_t P, CPN_HOST const int64_t *seg_offsets_host,
             const int64_t *seg_offsets_dev, int32_t nseg, float thresh, int64_t *keep, int32_t *keep_counts,
             void *workspace, int64_t workspace_bytes, void *stream);
 
@@ -409,7 +411,7 @@ int cpn_resize_f32(const float *src, float *dst, int64_t planes, int32_t Hin, in
  * CU counted) to out15[5 * bin + 0..4], bin 0 = 7x7 convs, 1 = 3x3, 2 = other tap counts.  out15 (host, may be NULL) receives the
  * sums, reset != 0 clears them afterwards.  The product library returns 1 ("built without the clock probe").  bench.py reports
  * shader MHz = 100 * ticks / ref ticks and matrix-pipe duty = pipe cycles / ticks next to the roofline. */
-int cpn_debug_clock_probe(unsigned long long *out15, int reset);
+int cpn_debug_clock_probe(CPN_HOST unsigned long long *out15, int reset);
 
 /* The same rule for ALL detections of a forwarded batch of tiles in one launch (the per-tile loop of
  * celldetection_scripts/cpn_inference.py:370-380): contour p belongs to image image_index[p] (int32, device);
@@ -430,7 +432,7 @@ int cpn_border_keep_batched(const float *contours, int64_t P, int32_t samples, c
  * convergence counter and the keep count back). */
 int64_t cpn_nms_binned_workspace_bytes(int64_t P, int64_t max_edges);
 int cpn_nms_binned(const float *boxes, const float *scores, int64_t P, float thresh, int64_t max_edges, int64_t *keep,
-                   int64_t *keep_count_dev, int64_t *keep_count_host, int64_t *edges_needed, int32_t *sweeps,
+                   int64_t *keep_count_dev, CPN_HOST int64_t *keep_count_host, CPN_HOST int64_t *edges_needed, CPN_HOST int32_t *sweeps,
                    void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Slide preprocessing before tiling: `preprocess` -> cd.data.normalize_percentile
@@ -480,7 +482,7 @@ int cpn_labels_round(const int32_t *points, const int32_t *boxes, int64_t K, int
                      int32_t gap, int32_t grid_w, int32_t grid_h, int32_t cell, const uint32_t *sorted_index,
                      const uint32_t *cell_begin, const uint32_t *cell_end, int32_t *canvas, int32_t channels,
                      uint8_t *state, uint8_t *ready, uint32_t *ready_list, int32_t *channel, int32_t *counters,
-                     int32_t *counters_host, int32_t use_ioa, double ioa_thresh, void *stream);
+                     CPN_HOST int32_t *counters_host, int32_t use_ioa, double ioa_thresh, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Instance evaluation of label images (cd.data.LabelMatcher, celldetection/data/instance_eval.py; csrc/instance_eval.hip).
@@ -504,7 +506,7 @@ int cpn_labels_round(const int32_t *points, const int32_t *boxes, int64_t K, int
 int64_t cpn_eval_workspace_bytes(int64_t table_capacity, int64_t pairs, int64_t labels);
 int cpn_eval_pairs(const int32_t *inputs, int32_t c_in, const int32_t *targets, int32_t c_t, int64_t pixels,
                    int64_t table_capacity, void *workspace, int64_t workspace_bytes, void *stream);
-int cpn_eval_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream);
+int cpn_eval_table_status(void *workspace, int64_t table_capacity, CPN_HOST int64_t *status_host, void *stream);
 int cpn_eval_compact(void *workspace, int64_t table_capacity, int64_t *keys, int64_t *counts, int64_t entries, void *stream);
 int cpn_eval_unions(const int64_t *pair_keys, const int64_t *intersections, int64_t pairs, const int64_t *input_labels,
                     const int64_t *input_counts, int64_t n_inputs, const int64_t *target_labels, const int64_t *target_counts,
@@ -512,7 +514,7 @@ int cpn_eval_unions(const int64_t *pair_keys, const int64_t *intersections, int6
                     void *stream);
 int cpn_eval_select(const int64_t *intersections, const int64_t *unions, const int32_t *input_index, const int32_t *target_index,
                     int64_t pairs, int64_t n_inputs, int64_t n_targets, double iou_thresh, uint8_t *selected, void *workspace,
-                    int64_t workspace_bytes, int64_t *result_host, void *stream);
+                    int64_t workspace_bytes, CPN_HOST int64_t *result_host, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Flat label images (cd.data.resolve_label_channels, celldetection/data/cpn.py:361-399; called from
@@ -538,9 +540,9 @@ int cpn_eval_select(const int64_t *intersections, const int64_t *unions, const i
 #define CPN_FLAT_MAX_STEPS 8
 int64_t cpn_flat_workspace_bytes(int32_t H, int32_t W);
 int cpn_flat_classify(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t plain_max, int32_t *lbl,
-                      void *workspace, int64_t workspace_bytes, int64_t *status_host, void *stream);
+                      void *workspace, int64_t workspace_bytes, CPN_HOST int64_t *status_host, void *stream);
 int cpn_flat_step(int32_t *lbl, int32_t H, int32_t W, int32_t steps, int32_t footprint, int32_t launch, void *workspace,
-                  int64_t workspace_bytes, int64_t *status_host, void *stream);
+                  int64_t workspace_bytes, CPN_HOST int64_t *status_host, void *stream);
 int cpn_flat_finish(int32_t *lbl, int32_t H, int32_t W, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
@@ -599,14 +601,14 @@ int cpn_flat_finish(int32_t *lbl, int32_t H, int32_t W, void *workspace, int64_t
 #define CPN_PROPS_I16 1
 #define CPN_PROPS_I32 2
 int64_t cpn_props_workspace_bytes(int64_t table_capacity, int32_t intensity_channels);
-int32_t cpn_props_columns(const int32_t *properties, int32_t n_properties, int32_t intensity_channels);
+int32_t cpn_props_columns(CPN_HOST const int32_t *properties, int32_t n_properties, int32_t intensity_channels);
 int cpn_props_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t channels, const void *intensity,
                          int32_t intensity_channels, int32_t intensity_dtype, int64_t table_capacity, void *workspace,
                          int64_t workspace_bytes, void *stream);
-int cpn_props_table_status(void *workspace, int64_t table_capacity, int64_t *status_host, void *stream);
+int cpn_props_table_status(void *workspace, int64_t table_capacity, CPN_HOST int64_t *status_host, void *stream);
 int cpn_props_compact_sort(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, void *stream);
 int cpn_props_finalise(void *workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries,
-                       const int32_t *properties, int32_t n_properties, double spacing_row, double spacing_col, int64_t *out,
+                       CPN_HOST const int32_t *properties, int32_t n_properties, double spacing_row, double spacing_col, int64_t *out,
                        int64_t out_columns, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
@@ -660,7 +662,7 @@ int cpn_props_finalise(void *workspace, int64_t table_capacity, int32_t intensit
 #define CPN_SHAPE_SOLIDITY 6
 #define CPN_SHAPE_COUNT 7
 int64_t cpn_shape_workspace_bytes(int64_t table_capacity);
-int32_t cpn_shape_columns(const int32_t *properties, int32_t n_properties);
+int32_t cpn_shape_columns(CPN_HOST const int32_t *properties, int32_t n_properties);
 int cpn_shape_heights(void *props_workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, int64_t *heights,
                       void *stream);
 int cpn_shape_accumulate(const int32_t *labels, int32_t H, int32_t W, int32_t channels, void *props_workspace, int64_t table_capacity,
@@ -670,7 +672,7 @@ int64_t cpn_shape_hull_scratch_bytes(int64_t entries, int64_t total_rows);
 int cpn_shape_hull(int64_t entries, const int64_t *row_begin, const uint32_t *extents, int64_t total_rows, void *scratch,
                    int64_t scratch_bytes, int64_t *counts, void *stream);
 int cpn_shape_finalise(void *props_workspace, int64_t table_capacity, int32_t intensity_channels, int64_t entries, void *workspace,
-                       const int64_t *hull_counts, const int32_t *properties, int32_t n_properties, double spacing_row,
+                       const int64_t *hull_counts, CPN_HOST const int32_t *properties, int32_t n_properties, double spacing_row,
                        double spacing_col, int64_t *out, int64_t out_columns, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
@@ -705,9 +707,9 @@ int cpn_overlay_bin_fill(const int32_t *boxes, int64_t K, int32_t H, int32_t W, 
                          int32_t *list, int64_t pairs, void *stream);
 int cpn_overlay_paint(const int32_t *points, const int32_t *boxes, const uint8_t *colors, int64_t K, int32_t S, int32_t H,
                       int32_t W, const int32_t *tile_begin, const int32_t *list, uint8_t *out, uint32_t *max_overlap,
-                      uint32_t *max_overlap_host, void *stream);
+                      CPN_HOST uint32_t *max_overlap_host, void *stream);
 int cpn_label_cmap(const int32_t *labels, int64_t pixels, int32_t channels, int32_t reduce, const uint8_t *table, int32_t rows,
-                   uint8_t *out, int32_t *flag, int32_t *flag_host, void *stream);
+                   uint8_t *out, int32_t *flag, CPN_HOST int32_t *flag_host, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Contours of label images (cd.data.labels2contours / labels2contour_list, celldetection/data/cpn.py:93-144, and
@@ -747,13 +749,13 @@ int cpn_label_cmap(const int32_t *labels, int64_t pixels, int32_t channels, int3
 #define CPN_CONTOURS_TILE 32
 int64_t cpn_contours_workspace_bytes(int64_t entries);
 int cpn_contours_components(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t *roots, void *workspace,
-                            int64_t workspace_bytes, int64_t *status_host, void *stream);
+                            int64_t workspace_bytes, CPN_HOST int64_t *status_host, void *stream);
 int cpn_contours_table(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t *roots, int64_t entries,
-                       int32_t *table, int32_t *frag_values, void *workspace, int64_t workspace_bytes, int64_t *status_host,
+                       int32_t *table, int32_t *frag_values, void *workspace, int64_t workspace_bytes, CPN_HOST int64_t *status_host,
                        void *stream);
 int cpn_contours_count(const int32_t *roots, int32_t channels, int32_t H, int32_t W, int64_t K, const int32_t *chan,
                        const int32_t *root, const int32_t *npix, int64_t *lengths, int64_t *offsets, void *workspace,
-                       int64_t workspace_bytes, int64_t *status_host, void *stream);
+                       int64_t workspace_bytes, CPN_HOST int64_t *status_host, void *stream);
 int cpn_contours_write(const int32_t *roots, int32_t channels, int32_t H, int32_t W, int64_t K, const int32_t *chan,
                        const int32_t *root, const int32_t *npix, const int64_t *offsets, int32_t *points, void *workspace,
                        int64_t workspace_bytes, void *stream);
@@ -800,7 +802,7 @@ int cpn_resample_contours(const double *points, const int64_t *offsets, int64_t 
 int64_t cpn_efd_workspace_bytes(int64_t K, int64_t P, int32_t order);
 int cpn_efd(const void *points, int32_t points_dtype, const int64_t *offsets, int64_t K, int64_t P, int32_t order, double epsilon,
             int32_t close_mode, void *workspace, int64_t workspace_bytes, double *coefficients_f64, double *locations_f64,
-            int64_t *status_host, void *stream);
+            CPN_HOST int64_t *status_host, void *stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * CPN training targets (cd.data.labels2distances / mask_labels_by_distance_, celldetection/data/cpn.py:424-497, and
@@ -843,12 +845,12 @@ int cpn_efd(const void *points, int32_t points_dtype, const int64_t *offsets, in
 int64_t cpn_label_distances_workspace_bytes(int32_t H, int32_t W);
 int64_t cpn_label_distances_table_bytes(int64_t table_capacity);
 int cpn_label_distances_classify(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t distance_type,
-                                 int32_t per_instance, void *workspace, int64_t workspace_bytes, int64_t *status_host,
+                                 int32_t per_instance, void *workspace, int64_t workspace_bytes, CPN_HOST int64_t *status_host,
                                  void *stream);
 int cpn_label_distances_step(int32_t H, int32_t W, int32_t steps, int32_t distance_type, int32_t per_instance, int32_t launch,
-                             void *workspace, int64_t workspace_bytes, int64_t *status_host, void *stream);
+                             void *workspace, int64_t workspace_bytes, CPN_HOST int64_t *status_host, void *stream);
 int cpn_label_distances_reduce(int32_t H, int32_t W, void *workspace, int64_t workspace_bytes, void *table,
-                               int64_t table_capacity, int64_t *status_host, void *stream);
+                               int64_t table_capacity, CPN_HOST int64_t *status_host, void *stream);
 int cpn_label_distances_finalise(const int32_t *labels, int32_t channels, int32_t H, int32_t W, int32_t per_instance,
                                  int32_t protected_size, void *workspace, int64_t workspace_bytes, const void *table,
                                  int64_t table_capacity, float *distances, int32_t *labels_out, void *stream);
@@ -1529,8 +1531,8 @@ typedef struct CpnOptimTensor {
     int32_t flags;   /* written by the upload */
     float lr, decay, w1, beta2, w2, eps, step_size, bc2_sqrt;
 } CpnOptimTensor;    /* 80 bytes */
-int cpn_optim_info(const int64_t *numel, int32_t n, int64_t info[3], int64_t *per_tensor);
-int cpn_optim_chunk_map(const int64_t *numel, int32_t n, int32_t *map, int64_t chunks);
+int cpn_optim_info(CPN_HOST const int64_t *numel, int32_t n, int64_t info[3], CPN_HOST int64_t *per_tensor);
+int cpn_optim_chunk_map(CPN_HOST const int64_t *numel, int32_t n, int32_t *map, int64_t chunks);
 int cpn_optim_upload(CpnOptimTensor *host, int32_t n, int32_t with_state, void *device, void *stream);
 int cpn_optim_sumsq(const void *table, int32_t n, const int32_t *map, int64_t chunks, double *partials, void *stream);
 int cpn_optim_norm(const double *partials, int64_t chunks, double max_norm, float *norm_coef, void *stream);

@@ -49,17 +49,11 @@ def image(size, objects, radius):
 def contours_components_ms(labels, repeats, lib_path=None, buffers=None):
     """lib_path: time this library's cpn_contours_components instead of the tree's (loaded next to it, its own kernels).
     buffers: a dict that keeps the roots image and the workspace from one call to the next (the same memory for both libraries)."""
-    import ctypes
     import torch
     from celldetection_amd import _lib
     from celldetection_amd._lib import ptr, stream_ptr
     from flat_labels_microbench import event_ms
-    lib = _lib.load()
-    if lib_path:
-        lib = ctypes.CDLL(lib_path)
-        for name, restype, argtypes in _lib._SIGNATURES:
-            if name in ('cpn_contours_workspace_bytes', 'cpn_contours_components'):
-                getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    lib = _lib.bind(lib_path) if lib_path else _lib.load()
 
     def check(rc, what):
         if rc != 0:
