@@ -120,3 +120,35 @@ def bf16_from_f64(x):
     _, e = np.frexp(x)
     e = np.maximum(e, -125)  # below 2^-126 the spacing is that of the subnormals
     return np.ldexp(np.rint(np.ldexp(x, 8 - e)), e - 8).astype(F)
+
+
+# ---- the checks of one step on the GPU's tensors (shared by tests/test_gpu_optim.py and tests/test_gpu_train_step.py)
+
+def np_of(t):
+    """torch tensor -> float32 array on the host (bf16 widens exactly)."""
+    return t.detach().float().cpu().numpy()
+
+
+def same(t, a):
+    """Whether the tensor holds exactly the float32 bits of ``a``."""
+    return np.array_equal(np_of(t).view(np.uint32), np.asarray(a, dtype=np.float32).view(np.uint32))
+
+
+def expect(h, bf16, step, hyper, coef=None):
+    """h: dict(p, g, m, v) of float32 arrays before the step -> (p, m, v) after it by the float32 rule; a bf16 parameter rounds once."""
+    p, m, v = step_f32(h['p'], h['g'], h['m'], h['v'], step=step, coef=coef, **hyper)
+    return (bf16_rne(p) if bf16 else p), m, v
+
+
+def assert_step(opt, params, host, bf16s, step, hyper, coef=None):
+    """Every parameter and both moments after ``opt.step()`` are the float32 rule bit for bit, the moments float32, the step count a
+    float32 CPU scalar, the gradient untouched.  host: per parameter dict(p, g, m, v) before the step; bf16s: per parameter, whether
+    it is bfloat16."""
+    for i, (p, h, bf16) in enumerate(zip(params, host, bf16s)):
+        want = expect(h, bf16, step, hyper, coef)
+        state = opt.state[p]
+        assert str(state['exp_avg'].dtype) == str(state['exp_avg_sq'].dtype) == 'torch.float32' and float(state['step']) == step
+        assert state['step'].device.type == 'cpu' and str(state['step'].dtype) == 'torch.float32'
+        for name, got, w in zip('pmv', (p, state['exp_avg'], state['exp_avg_sq']), want):
+            assert same(got, w), (i, p.numel(), bf16, name, float(np.abs(np_of(got) - w).max()))
+        assert same(p.grad, h['g']), i  # the gradient is read, never written

@@ -52,28 +52,15 @@ def _set_state(opt, params, host, step):
         opt.state[p] = dict(step=torch.tensor(float(step), dtype=F32), exp_avg=_dev(h['m']), exp_avg_sq=_dev(h['v']))
 
 
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
-def _same(t, a):
-    return np.array_equal(_np(t).view(np.uint32), np.asarray(a, dtype=np.float32).view(np.uint32))
+_np, _same = oracle.np_of, oracle.same  # (the checks of one step live in tests/optim_oracle.py: the training-step tests share them)
 
 
 def _expect(h, dt, step, hyper=HYPER, coef=None):
-    p, m, v = oracle.step_f32(h['p'], h['g'], h['m'], h['v'], step=step, coef=coef, **hyper)
-    return (oracle.bf16_rne(p) if dt == BF16 else p), m, v
+    return oracle.expect(h, dt == BF16, step, hyper, coef)
 
 
 def _assert_step(opt, params, host, dtypes, step, hyper=HYPER, coef=None):
-    for i, (p, h, dt) in enumerate(zip(params, host, dtypes)):
-        want = _expect(h, dt, step, hyper, coef)
-        state = opt.state[p]
-        assert state['exp_avg'].dtype == F32 and state['exp_avg_sq'].dtype == F32 and float(state['step']) == step
-        assert state['step'].device.type == 'cpu' and state['step'].dtype == F32
-        for name, got, w in zip('pmv', (p, state['exp_avg'], state['exp_avg_sq']), want):
-            assert _same(got, w), (i, p.numel(), dt, name, float(np.abs(_np(got) - w).max()))
-        assert _same(p.grad, h['g']), i  # the gradient is read, never written
+    oracle.assert_step(opt, params, host, [dt == BF16 for dt in dtypes], step, hyper, coef)
 
 
 @pytest.mark.parametrize('kind', list(LISTS))
