@@ -62,8 +62,12 @@ CASES = {
 
 # (the ids keep the suffix they had while a second tile existed, so that a case's history stays under one id)
 @pytest.mark.parametrize('name', list(CASES), ids=[f'{n}-one_workgroup_per_cu' for n in CASES])
-def test_conv_bridge_kernel(dev, name):
-    """The fused kernel (MODE_BR, the <16,64,2,2> tile) against the two launches it replaces, and both against the fp64 conv."""
+def test_conv_bridge_kernel(dev, name, embed=None):
+    """The fused kernel (MODE_BR, the <16,64,2,2> tile) against the two launches it replaces, and both against the fp64 conv.
+    ``embed`` (tests/test_gpu_read_guards.py; a byte pattern of tests/read_guards.py): the source lies between bands of that
+    pattern, which must come back intact around the unchanged source, the library must have received exactly that pointer, and
+    the stored results are returned after all of the above."""
+    import read_guards as rg
     from celldetection_amd import _lib, graph
     from celldetection_amd.subpixel import collapse_upsampled_taps, phase_padding
     cfg = dict(seed=0)
@@ -77,10 +81,13 @@ def test_conv_bridge_kernel(dev, name):
     d0 = torch.zeros(n, h, w, cs, dtype=torch.bfloat16, device=dev)
     d0[..., :cin] = x.permute(0, 2, 3, 1).to(torch.bfloat16).to(dev)
     lib = _lib.load()
+    e = rg.Embedding(embed)
+    d0 = e('src', d0)
     H, W = 2 * h, 2 * w
     fused, fbuf, fg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
-    _lib.check(lib.cpn_conv_bridge(ops[2], _lib.ptr(d0), cs, None, 0, _lib.ptr(fused), 64, n, h, w, _lib.ptr(wblob),
-                                   _lib.ptr(bblob), _lib.stream_ptr()), 'conv_bridge')
+    with e.watch(lib, 'cpn_conv_bridge'):
+        _lib.check(lib.cpn_conv_bridge(ops[2], _lib.ptr(d0), cs, None, 0, _lib.ptr(fused), 64, n, h, w, _lib.ptr(wblob),
+                                       _lib.ptr(bblob), _lib.stream_ptr()), 'conv_bridge')
     mid, mbuf, mg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
     two, tbuf, tg = cb.guarded_nhwc_bf16(n, H, W, 64, dev)
     # the scattered phase conv takes the LOW-resolution size, the 3x3 conv the full-resolution one
@@ -89,6 +96,7 @@ def test_conv_bridge_kernel(dev, name):
     _lib.check(lib.cpn_conv2d(ops[1], _lib.ptr(mid), 64, None, 0, None, 0, _lib.ptr(two), 64, n, H, W, _lib.ptr(wblob),
                               _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d 3x3')
     torch.cuda.synchronize()
+    e.check()
     got = cb.assert_nhwc_bf16('conv_bridge', fbuf, fg, fused, 64)
     got_mid = cb.assert_nhwc_bf16('scatter launch', mbuf, mg, mid, 64)
     got_two = cb.assert_nhwc_bf16('3x3 launch', tbuf, tg, two, 64)
@@ -110,6 +118,8 @@ def test_conv_bridge_kernel(dev, name):
     ref2, S2, d2 = cb.conv_with_noise(got_mid, w2.to(torch.bfloat16), b2.to(torch.float32), 1, 1, n=cb.chain_length(3, 3, 64))
     r2 = cb.check(f'{name} 3x3', got_two, *cb.bf16_bounds(ref2, d2, 'relu'), F.relu(ref2), S2)
     print(f'{name}: max |got - ref| / bound: scatter {r1:.3g}, 3x3 {r2:.3g}')
+    if e:
+        return dict(bridge=got, scatter=got_mid, two_launches=got_two)
 
 
 def test_conv_bridge_in_the_plan_and_switch(dev, monkeypatch):

@@ -49,7 +49,10 @@ def _pair_plan(cin, cmid, groups, seed, stride=1):
     return P, sd
 
 
-def run_pair(dev, *, n, h, w, cin, cmid, groups=32, seed=0, stride=1):
+def run_pair(dev, *, n, h, w, cin, cmid, groups=32, seed=0, stride=1, embed=None):
+    """``embed``: a byte pattern of tests/read_guards.py; the source then lies between bands of that pattern, which must come back
+    intact around the unchanged source, and the library must have received exactly that pointer."""
+    import read_guards as rg
     from celldetection_amd import _lib, graph
     P, sd = _pair_plan(cin, cmid, groups, seed, stride)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
@@ -60,16 +63,20 @@ def run_pair(dev, *, n, h, w, cin, cmid, groups=32, seed=0, stride=1):
     d0 = torch.zeros(n, h, w, cs, dtype=torch.bfloat16, device=dev)
     d0[..., :cin] = x.permute(0, 2, 3, 1).to(torch.bfloat16).to(dev)
     lib = _lib.load()
+    e = rg.Embedding(embed)
+    d0 = e('src', d0)
     cm = _pad32(cmid)
     fused, fbuf, fg = cb.guarded_nhwc_bf16(n, ho, wo, cm, dev)
-    _lib.check(lib.cpn_conv_pair(ops[2], _lib.ptr(d0), cs, _lib.ptr(fused), cm, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob),
-                                 _lib.stream_ptr()), 'conv_pair')
+    with e.watch(lib, 'cpn_conv_pair'):
+        _lib.check(lib.cpn_conv_pair(ops[2], _lib.ptr(d0), cs, _lib.ptr(fused), cm, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob),
+                                     _lib.stream_ptr()), 'conv_pair')
     mid, mbuf, mg = cb.guarded_nhwc_bf16(n, h, w, cm, dev)
     two, tbuf, tg = cb.guarded_nhwc_bf16(n, ho, wo, cm, dev)
     for op, src, dst, ss in ((ops[0], d0, mid, cs), (ops[1], mid, two, cm)):
         _lib.check(lib.cpn_conv2d(op, _lib.ptr(src), ss, None, 0, None, 0, _lib.ptr(dst), cm, n, h, w, _lib.ptr(wblob),
                                   _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d')
     torch.cuda.synchronize()
+    e.check()
     got_fused = cb.assert_nhwc_bf16('conv_pair', fbuf, fg, fused, cmid)
     got_mid = cb.assert_nhwc_bf16('first launch', mbuf, mg, mid, cmid)
     got_two = cb.assert_nhwc_bf16('second launch', tbuf, tg, two, cmid)

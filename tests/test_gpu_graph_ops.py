@@ -14,6 +14,7 @@ import torch
 
 import conv_bounds as cb
 import graph_ops_oracle as go
+import read_guards as rg
 from celldetection_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -101,43 +102,54 @@ def plan_result(dev, prec, ops, x, scales=None, read=None):
 
 
 # ---- the bf16 entry points, into guarded buffers -------------------------------------------------------------------------------------
-def direct_pool(dev, x, k, s, p):
+# (``embed``: a byte pattern of tests/read_guards.py; the source then lies between bands of that pattern, which must come back intact
+# around the unchanged source, and the library must have received exactly that pointer)
+def direct_pool(dev, x, k, s, p, embed=None):
     lib = _lib.load()
     n, c, h, w = x.shape
     ho, wo = go.chain_size((h, w), ((k, s, p),))
-    src = stored('bf16', x).to(dev)
+    e = rg.Embedding(embed)
+    src = e('src', stored('bf16', x).to(dev))
     out, buf, guard = cb.guarded_nhwc_bf16(n, ho, wo, c, dev)
-    _lib.check(lib.cpn_maxpool2d(_lib.ptr(src), _lib.ptr(out), n, h, w, c, k, s, p, _lib.stream_ptr()), 'maxpool2d')
+    with e.watch(lib, 'cpn_maxpool2d'):
+        _lib.check(lib.cpn_maxpool2d(_lib.ptr(src), _lib.ptr(out), n, h, w, c, k, s, p, _lib.stream_ptr()), 'maxpool2d')
     torch.cuda.synchronize()
+    e.check()
     cb.assert_guards(f'maxpool {k}/{s}/{p}', buf, guard, cb.BF16_GUARD)
     return out.cpu()
 
 
-def direct_resize(dev, x, size):
+def direct_resize(dev, x, size, embed=None):
     lib = _lib.load()
     n, c, h, w = x.shape
-    src = stored('bf16', x).to(dev)
+    e = rg.Embedding(embed)
+    src = e('src', stored('bf16', x).to(dev))
     out, buf, guard = cb.guarded_nhwc_bf16(n, size[0], size[1], c, dev)
-    _lib.check(lib.cpn_resize_bilinear(_lib.ptr(src), _lib.ptr(out), n, h, w, size[0], size[1], c, _lib.stream_ptr()), 'resize_bilinear')
+    with e.watch(lib, 'cpn_resize_bilinear'):
+        _lib.check(lib.cpn_resize_bilinear(_lib.ptr(src), _lib.ptr(out), n, h, w, size[0], size[1], c, _lib.stream_ptr()), 'resize_bilinear')
     torch.cuda.synchronize()
+    e.check()
     cb.assert_guards(f'resize {h}x{w}->{size}', buf, guard, cb.BF16_GUARD)
     return out.cpu()
 
 
-def direct_input(dev, x, cpad, stem=False):
+def direct_input(dev, x, cpad, stem=False, embed=None):
     """-> (stored tensor with its padded channels | the stem record, range flag)"""
     lib = _lib.load()
     n, c, h, w = x.shape
-    src = x.contiguous().to(dev)
+    e = rg.Embedding(embed)
+    src = e('src', x.contiguous().to(dev))
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     dtype = 1 if x.dtype == torch.uint8 else 0
-    if stem:
-        out, buf, guard = cb.guarded_nhwc_bf16(n, h + 6, w + 8, 4, dev)
-        _lib.check(lib.cpn_convert_input_stem(_lib.ptr(src), dtype, _lib.ptr(out), n, c, h, w, _lib.ptr(flag), _lib.stream_ptr()), 'input_stem')
-    else:
-        out, buf, guard = cb.guarded_nhwc_bf16(n, h, w, cpad, dev)
-        _lib.check(lib.cpn_convert_input(_lib.ptr(src), dtype, _lib.ptr(out), n, c, h, w, cpad, _lib.ptr(flag), _lib.stream_ptr()), 'input')
+    with e.watch(lib, 'cpn_convert_input_stem', 'cpn_convert_input'):
+        if stem:
+            out, buf, guard = cb.guarded_nhwc_bf16(n, h + 6, w + 8, 4, dev)
+            _lib.check(lib.cpn_convert_input_stem(_lib.ptr(src), dtype, _lib.ptr(out), n, c, h, w, _lib.ptr(flag), _lib.stream_ptr()), 'input_stem')
+        else:
+            out, buf, guard = cb.guarded_nhwc_bf16(n, h, w, cpad, dev)
+            _lib.check(lib.cpn_convert_input(_lib.ptr(src), dtype, _lib.ptr(out), n, c, h, w, cpad, _lib.ptr(flag), _lib.stream_ptr()), 'input')
     torch.cuda.synchronize()
+    e.check()
     cb.assert_guards('input conversion', buf, guard, cb.BF16_GUARD)
     return out.cpu(), int(flag.item())
 

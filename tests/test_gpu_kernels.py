@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_bounds as cb
+import read_guards as rg
 
 pytestmark = pytest.mark.gpu
 
@@ -84,8 +85,10 @@ def random_state_dict(P, g):
 
 def run_conv(dev, *, n, h, w, cin, cout, k, stride=1, groups=1, bias=True, bn=True, act='relu', cin1=0, up0=False,
              up1=False, res=False, res_up=False, out_f32=False, act_scale=3., seed=0, fuse_cout=0, fuse_act='none',
-             bilinear=False, reference=True):
+             bilinear=False, reference=True, embed=None):
     """Builds a one-conv plan, runs cpn_conv2d -> (got as fp32 NCHW CPU tensor, bound check or None, out_f32).
+    ``embed``: a byte pattern of tests/read_guards.py; the two sources and the residual then lie between bands of that pattern,
+    which must come back intact around unchanged operands, and the library must have received exactly those pointers.
 
     The output lies in a buffer with guard bands (a whole output row before and after bf16 NHWC outputs, a whole plane
     around fp32 NCHW ones) that must come back untouched; the padded channels cout..cpad of a bf16 output must be zeros
@@ -114,6 +117,8 @@ def run_conv(dev, *, n, h, w, cin, cout, k, stride=1, groups=1, bias=True, bn=Tr
     d1 = to_nhwc_bf16(x1.to(dev)) if cin1 else None
     dr = to_nhwc_bf16(xr.to(dev)) if res else None
     lib = _lib.load()
+    e = rg.Embedding(embed)
+    d0, d1, dr = e('src0', d0), e('src1', d1), e('res', dr)
     cout_out = fuse_cout or cout
     if out_f32:
         guard, sentinel = ho * wo, F32_GUARD
@@ -123,11 +128,13 @@ def run_conv(dev, *, n, h, w, cin, cout, k, stride=1, groups=1, bias=True, bn=Tr
         guard, sentinel = wo * _pad32(cout), BF16_GUARD
         dst, buf = guarded((n, ho, wo, _pad32(cout)), torch.bfloat16, guard, sentinel, dev)
         dstride = _pad32(cout)
-    _lib.check(lib.cpn_conv2d(op, _lib.ptr(d0), d0.shape[-1], _lib.ptr(d1), 0 if d1 is None else d1.shape[-1],
-                              _lib.ptr(dr), 0 if dr is None else dr.shape[-1], _lib.ptr(dst), dstride, n, hin, win,
-                              _lib.ptr(wblob), _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d')
+    with e.watch(lib, 'cpn_conv2d'):
+        _lib.check(lib.cpn_conv2d(op, _lib.ptr(d0), d0.shape[-1], _lib.ptr(d1), 0 if d1 is None else d1.shape[-1],
+                                  _lib.ptr(dr), 0 if dr is None else dr.shape[-1], _lib.ptr(dst), dstride, n, hin, win,
+                                  _lib.ptr(wblob), _lib.ptr(bblob), _lib.stream_ptr()), 'conv2d')
     torch.cuda.synchronize()
     assert_guards('conv2d', buf, guard, sentinel)
+    e.check()
     if out_f32:
         got = dst.cpu()
     else:
@@ -318,12 +325,14 @@ def subpixel_plan(c):
 
 
 @pytest.mark.parametrize('name', list(SUBPIXEL_CASES))
-def test_subpixel_decoder_conv(dev, name):
+def test_subpixel_decoder_conv(dev, name, embed=None):
     """Sub-pixel triple of a UNet decoder conv over cat(lateral, nearest-x2-upsampled top-down map)
     (models/unet.py:213-224): PHASE (four 2x2 convs on the low-resolution map) + LATERAL (3x3 on the lateral, pixel-
     shuffled partial sums as residual) against (a) an fp32 emulation of exactly that arithmetic on the same bf16-rounded
     operands -- tap sums rounded to bf16 ONCE, partial sums rounded to bf16 -- and (b) the HEAD conv = the reference's
-    statement of the layer (both approximate the fp32 conv; they differ by the rounding of the tap sums and partials)."""
+    statement of the layer (both approximate the fp32 conv; they differ by the rounding of the tap sums and partials).
+    ``embed`` (tests/test_gpu_read_guards.py; a byte pattern of tests/read_guards.py): both sources lie between bands of that
+    pattern, checked as in run_conv, and the three stored results are returned after all of the above."""
     from celldetection_amd import _lib, graph
     from celldetection_amd.subpixel import collapse_upsampled_taps, phase_padding
     c = dict(bias=True, seed=0)
@@ -336,19 +345,23 @@ def test_subpixel_decoder_conv(dev, name):
     xl = torch.randn(n, c0, h, w, generator=g).to(torch.bfloat16).float()
     xt = torch.randn(n, c1, h // 2, w // 2, generator=g).to(torch.bfloat16).float()
     dl, dt = to_nhwc_bf16(xl.to(dev)), to_nhwc_bf16(xt.to(dev))
+    e = rg.Embedding(embed)
+    dl, dt = e('lateral', dl), e('top', dt)
     cp = _pad32(cout)
     lib = _lib.load()
     head, hbuf, hg = cb.guarded_nhwc_bf16(n, h, w, cp, dev)
     part, pbuf, pg = cb.guarded_nhwc_bf16(n, h // 2, w // 2, 4 * cp, dev)
     pair, qbuf, qg = cb.guarded_nhwc_bf16(n, h, w, cp, dev)
     args = (_lib.ptr(wblob), _lib.ptr(bblob), _lib.stream_ptr())
-    _lib.check(lib.cpn_conv2d(ops[0], _lib.ptr(dl), dl.shape[-1], _lib.ptr(dt), dt.shape[-1], _lib.ptr(None), 0,
-                              _lib.ptr(head), cp, n, h, w, *args), 'head')
-    _lib.check(lib.cpn_conv2d(ops[1], _lib.ptr(dt), dt.shape[-1], _lib.ptr(None), 0, _lib.ptr(None), 0,
-                              _lib.ptr(part), 4 * cp, n, h // 2, w // 2, *args), 'phase')
-    _lib.check(lib.cpn_conv2d(ops[2], _lib.ptr(dl), dl.shape[-1], _lib.ptr(None), 0, _lib.ptr(part), 4 * cp,
-                              _lib.ptr(pair), cp, n, h, w, *args), 'lateral')
+    with e.watch(lib, 'cpn_conv2d'):
+        _lib.check(lib.cpn_conv2d(ops[0], _lib.ptr(dl), dl.shape[-1], _lib.ptr(dt), dt.shape[-1], _lib.ptr(None), 0,
+                                  _lib.ptr(head), cp, n, h, w, *args), 'head')
+        _lib.check(lib.cpn_conv2d(ops[1], _lib.ptr(dt), dt.shape[-1], _lib.ptr(None), 0, _lib.ptr(None), 0,
+                                  _lib.ptr(part), 4 * cp, n, h // 2, w // 2, *args), 'phase')
+        _lib.check(lib.cpn_conv2d(ops[2], _lib.ptr(dl), dl.shape[-1], _lib.ptr(None), 0, _lib.ptr(part), 4 * cp,
+                                  _lib.ptr(pair), cp, n, h, w, *args), 'lateral')
     torch.cuda.synchronize()
+    e.check()
     got_head = cb.assert_nhwc_bf16('head', hbuf, hg, head, cout)
     got = cb.assert_nhwc_bf16('lateral', qbuf, qg, pair, cout)
     cb.assert_guards('phase', pbuf, pg, cb.BF16_GUARD)
@@ -382,6 +395,8 @@ def test_subpixel_decoder_conv(dev, name):
     rel_head = ((got_head - full).norm() / full.norm()).item()
     print(f'{name}: rel L2 vs the fp32 conv: sub-pixel pair {rel_pair:.2e}, head conv {rel_head:.2e}')
     assert rel_pair < 1e-2 and rel_pair < 2.5 * rel_head + 1e-3
+    if e:
+        return dict(head=got_head, partial_sums=got_part, lateral=got)
 
 
 @pytest.mark.parametrize('n,h,w,cin,cout,bias', [(2, 32, 32, 64, 64, False), (1, 40, 72, 16, 24, True),
@@ -433,9 +448,12 @@ def test_subpixel_bridge_conv(dev, n, h, w, cin, cout, bias):
 
 @pytest.mark.parametrize('n,h,w,cin,cout,dtype', [(2, 64, 96, 3, 64, 0), (1, 75, 101, 3, 64, 0), (3, 33, 47, 1, 8, 1),
                                                    (2, 64, 64, 4, 32, 0), (16, 128, 128, 3, 64, 1), (1, 7, 9, 3, 64, 0)])
-def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
+def test_stem_fast_path(dev, n, h, w, cin, cout, dtype, embed=None):
     """csrc/stem.hip: ResNet stem conv 7x7 stride 2 pad 3 + BN + ReLU (models/resnet.py:274-284) from the padded 4-channel
-    input layout, against an fp32 conv on the same bf16-rounded operands; the input conversion itself must be exact."""
+    input layout, against an fp32 conv on the same bf16-rounded operands; the input conversion itself must be exact.
+    ``embed`` (tests/test_gpu_read_guards.py; a byte pattern of tests/read_guards.py): the image, the padded record (which the
+    input conversion is documented to write) and the generic kernel's source lie between bands of that pattern, checked as in
+    run_conv, and the stored results are returned after all of the above."""
     from celldetection_amd import _lib, graph
     g = torch.Generator().manual_seed(h * 1000 + w)
     P = graph.Plan()
@@ -456,12 +474,14 @@ def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
     tens, ops, wblob, bblob = graph.pack(P, sd, dev)
     lib = _lib.load()
     xin = torch.rand(n, cin, h, w, generator=g)
-    src = xin.to(dev) if dtype == 0 else (xin * 255).to(torch.uint8).to(dev)
+    e = rg.Embedding(embed)
+    src = e('image', (xin.to(dev) if dtype == 0 else (xin * 255).to(torch.uint8).to(dev)).contiguous())
     xq = xin if dtype == 0 else (xin * 255).to(torch.uint8).float() / 255
-    pad = torch.full((n, h + 6, w + 8, 4), 7., dtype=torch.bfloat16, device=dev)
+    pad = e('stem record', torch.full((n, h + 6, w + 8, 4), 7., dtype=torch.bfloat16, device=dev), updated=True)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.cpn_convert_input_stem(_lib.ptr(src.contiguous()), dtype, _lib.ptr(pad), n, cin, h, w, _lib.ptr(flag),
-                                          _lib.stream_ptr()), 'input_stem')
+    with e.watch(lib, 'cpn_convert_input_stem'):
+        _lib.check(lib.cpn_convert_input_stem(_lib.ptr(src.contiguous()), dtype, _lib.ptr(pad), n, cin, h, w, _lib.ptr(flag),
+                                              _lib.stream_ptr()), 'input_stem')
     torch.cuda.synchronize()
     exp = torch.zeros(n, h + 6, w + 8, 4)
     exp[:, 3:3 + h, 3:3 + w, :cin] = xq.to(torch.bfloat16).float().permute(0, 2, 3, 1)
@@ -469,13 +489,14 @@ def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     cp = _pad32(cout)
     out, obuf, og = cb.guarded_nhwc_bf16(n, ho, wo, cp, dev)
-    _lib.check(lib.cpn_stem7(ops[3], _lib.ptr(pad), _lib.ptr(out), cp, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob), 0.,
-                             _lib.stream_ptr()), 'stem7')
     # the generic kernel on the 32-channel input, same weights: both against the same bound
-    gen_in = to_nhwc_bf16(xq.to(dev))
+    gen_in = e('generic source', to_nhwc_bf16(xq.to(dev)))
     gen, gbuf, gg = cb.guarded_nhwc_bf16(n, ho, wo, cp, dev)
-    _lib.check(lib.cpn_conv2d(ops[2], _lib.ptr(gen_in), gen_in.shape[-1], _lib.ptr(None), 0, _lib.ptr(None), 0, _lib.ptr(gen),
-                              cp, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob), _lib.stream_ptr()), 'generic stem')
+    with e.watch(lib, 'cpn_stem7', 'cpn_conv2d'):
+        _lib.check(lib.cpn_stem7(ops[3], _lib.ptr(pad), _lib.ptr(out), cp, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob), 0.,
+                                 _lib.stream_ptr()), 'stem7')
+        _lib.check(lib.cpn_conv2d(ops[2], _lib.ptr(gen_in), gen_in.shape[-1], _lib.ptr(None), 0, _lib.ptr(None), 0, _lib.ptr(gen),
+                                  cp, n, h, w, _lib.ptr(wblob), _lib.ptr(bblob), _lib.stream_ptr()), 'generic stem')
     torch.cuda.synchronize()
     got = cb.assert_nhwc_bf16('stem7', obuf, og, out, cout)
     got_gen = cb.assert_nhwc_bf16('generic stem', gbuf, gg, gen, cout)
@@ -494,6 +515,7 @@ def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
     _lib.check(lib.cpn_stem7(ops8[3], _lib.ptr(pad), _lib.ptr(codes), cp8, n, h, w, _lib.ptr(wblob8), _lib.ptr(bblob8),
                              1. / scale, _lib.stream_ptr()), 'stem7 fp8')
     torch.cuda.synchronize()
+    e.check()
     assert_guards('stem7 fp8', cbuf, wo * cp8, 0x7f)
     c8 = codes.cpu()
     assert bool(((c8[..., cout:] == 0) | (c8[..., cout:] == 0x80)).all()), 'stem7 fp8: padded output codes not zero'
@@ -506,6 +528,8 @@ def test_stem_fast_path(dev, n, h, w, cin, cout, dtype):
         _lib.check(lib.cpn_convert_input_stem(_lib.ptr(bad_in.to(dev)), 0, _lib.ptr(pad), n, cin, h, w, _lib.ptr(flag),
                                               _lib.stream_ptr()), 'input_stem')
         assert flag.item() == 1
+    if e:
+        return {'stem7': got, 'generic stem': got_gen, 'stem7 e4m3 codes': c8, 'stem record': pad.cpu()}
 
 
 @pytest.mark.parametrize('name', ['1x1_flagship_tile', '1x1_flagship_tile_res'])
@@ -767,7 +791,9 @@ def run_conv_fp8(dev, name, **cfg):
     tests/conv_bounds.py -- e4m3 outputs one of the codes RNE can produce from the accumulation-noise window, at the
     output's code scale; fp32 outputs within the noise + 4 ulp.  No allowance.  Guard rows around the output come back
     untouched, and every padded output code is a zero (0x00 or 0x80).  -> max |got - ref| / bound; a BoundError carries
-    .got / .lo / .hi / .ref (NCHW) for the caller's report."""
+    .got / .lo / .hi / .ref (NCHW) for the caller's report.
+    ``embed`` (a byte pattern of tests/read_guards.py): the sources and the residual lie between bands of that pattern, checked as
+    in run_conv; ``reference=False`` then returns the stored output as it is instead of judging it."""
     from celldetection_amd import _lib, graph
     n, h, w, cin, cout, k = (cfg[x] for x in ('n', 'h', 'w', 'cin', 'cout', 'k'))
     stride, groups, cin1, up1 = cfg.get('stride', 1), cfg.get('groups', 1), cfg.get('cin1', 0), cfg.get('up1', False)
@@ -788,6 +814,8 @@ def run_conv_fp8(dev, name, **cfg):
     d0, x0q = _to_nhwc_fp8(x0.to(dev), scales[s0], p64(cin))
     d1, x1q = _to_nhwc_fp8(x1.to(dev), scales[s1], p64(cin1)) if cin1 else (None, None)
     dr, xrq = _to_nhwc_fp8(xr.to(dev), scales[r], p64(cout)) if res else (None, None)
+    e = rg.Embedding(cfg.get('embed'))
+    d0, d1, dr = e('src0', d0), e('src1', d1), e('res', dr)
     # reference on the dequantised operands; the weight codes come from the packer (dequantised through mult)
     wf, bf = graph._fold(sd, P.ops[0])
     xin = x0q.cpu()
@@ -814,12 +842,16 @@ def run_conv_fp8(dev, name, **cfg):
         guard, sentinel = wo * p64(cout), 0x7f
         dst, buf = guarded((n, ho, wo, p64(cout)), torch.uint8, guard, sentinel, dev)
         dstride = p64(cout)
-    _lib.check(lib.cpn_conv2d_fp8(op, _lib.ptr(d0), d0.shape[-1], _lib.ptr(d1), 0 if d1 is None else d1.shape[-1],
-                                  _lib.ptr(dr), 0 if dr is None else dr.shape[-1], _lib.ptr(dst), dstride, n, h, w,
-                                  _lib.ptr(wblob), _lib.ptr(bblob), _lib.ptr(mblob), op_scales[0][0], op_scales[0][1],
-                                  _lib.stream_ptr()), 'conv2d_fp8')
+    with e.watch(lib, 'cpn_conv2d_fp8'):
+        _lib.check(lib.cpn_conv2d_fp8(op, _lib.ptr(d0), d0.shape[-1], _lib.ptr(d1), 0 if d1 is None else d1.shape[-1],
+                                      _lib.ptr(dr), 0 if dr is None else dr.shape[-1], _lib.ptr(dst), dstride, n, h, w,
+                                      _lib.ptr(wblob), _lib.ptr(bblob), _lib.ptr(mblob), op_scales[0][0], op_scales[0][1],
+                                      _lib.stream_ptr()), 'conv2d_fp8')
     torch.cuda.synchronize()
     assert_guards(name, buf, guard, sentinel)
+    e.check()
+    if not cfg.get('reference', True):
+        return dst.cpu()
     # the kernel: acc = sum of code products (exact in fp32), v = acc * mult + bias (+ code_r * res_scale), relu,
     # then RNE(sat(v * out_inv_scale)) -- mult, res_scale and out_inv_scale as the fp32 values it receives
     f32_ = lambda v: float(np.float32(v))
