@@ -6,8 +6,9 @@ loop.  Everything computes in hand-written HIP kernels behind the C ABI of ``lib
 (``include/cpn_hip.h``); there is no CPU fallback.
 """
 from . import cpn as models  # ``cd.models.CpnResNeXt101UNet`` -> ``celldetection_amd.models.CpnResNeXt101UNet``
-from . import (components, flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, nn, objective, ops, optim, overlay, preprocess, region_props, shape_props, synth,
+from . import (augment, components, flat_labels, fourier, h5, inference, instance_eval, label_contours, labels, nn, objective, ops, optim, overlay, preprocess, region_props, shape_props, synth,
                targets, util)
+from .augment import RandomAffine
 from .components import (fill_label_gaps_, label_components, masks2labels, relabel_, remove_partials_, rgb_to_scalar, stack_labels,
                          unary_masks2labels)
 from .flat_labels import resolve_label_channels
@@ -33,4 +34,4 @@ __all__ = ['models', 'ops', 'util', 'synth', 'inference', 'labels', 'contours2la
            'labels2fourier', 'targets', 'labels2distances', 'mask_labels_by_distance_', 'filter_instances_', 'CPNTargetGenerator',
            'objective', 'CPNObjective', 'collate_cpn_targets', 'components', 'label_components', 'relabel_', 'stack_labels',
            'rgb_to_scalar', 'unary_masks2labels', 'masks2labels', 'fill_label_gaps_', 'remove_partials_', 'nn',
-           'optim', 'AdamW', 'clip_grad_norm_', 'grad_norm', 'step_info']
+           'optim', 'AdamW', 'clip_grad_norm_', 'grad_norm', 'step_info', 'augment', 'RandomAffine']

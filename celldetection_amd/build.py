@@ -71,6 +71,9 @@ SOURCES = {
     # the optimizer step (global gradient norm, clip, AdamW): fp64 sums in a fixed order and an fp32 update defined operation by
     # operation (partition and lane mapping: csrc/optim_chunks.h): no FMA contraction, correctly rounded division and square root
     'optim.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+    # training augmentation: the joint affine warp of image and labels; the fp64 position and the fp32 blend are defined by their
+    # order of operations (index and weight arithmetic: csrc/warp_rule.h): no FMA contraction
+    'augment.hip': ['-ffp-contract=off'],
     'sparse_heads.hip': [],
     'stem.hip': [],
     # the native graph executor (host code only; cpn_plan.h names the units)
@@ -79,7 +82,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'optim_chunks.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'optim_chunks.h', 'warp_rule.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

@@ -1458,6 +1458,76 @@ int cpn_resized_conv_wgrad(const void *x, const void *dy, int32_t N, int32_t H, 
 int cpn_bilinear_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, void *dst, int32_t h, int32_t w, void *stream);
 int cpn_bilinear_sum_f32(const float *t, int64_t planes, int32_t H, int32_t W, float *dst, int32_t h, int32_t w, void *stream);
 
+/* ---- Augmentation warp --------------------------------------------------------------------------------------
+ * What celldetection_amd.augment (warp, RandomAffine) runs on: one launch that warps a batch of channels-last images and their
+ * [H, W, C] label stacks together, every sample by its own affine map, into the model's input layout and the label layout of
+ * celldetection_amd.relabel_ and celldetection_amd.CPNTargetGenerator.feed (csrc/augment.hip, csrc/warp_rule.h).  It stands for the
+ * albumentations pipeline of the reference's training recipe (Transpose, RandomRotate90, rotations and scalings, random crops,
+ * RandomGamma / RandomBrightnessContrast, normalisation; celldetection/data/misc.py random_crop).  albumentations and
+ * cv2.warpAffine are third-party, unpinned and absent here: their documented behaviour is restated, and their fixed-point
+ * interpolation tables (cv2's 5-bit coordinate fraction and 15-bit weights) are deliberately NOT copied.  The independent anchor is
+ * torch's float64 CPU grid_sample(align_corners=True), whose convention this is.  An addition to ABI 22.  This text is the contract.
+ *
+ * Coordinates.  Pixel centres lie at integer coordinates.  The map of a sample is six fp64 numbers m0 ... m5 that take a
+ * DESTINATION pixel to a SOURCE position: for destination row i and column j, each converted exactly to double,
+ *     sx = (m0 * j + m1 * i) + m2,      sy = (m3 * j + m4 * i) + m5,
+ * every operation rounded to fp64, no contraction (the unit is compiled with -ffp-contract=off).
+ *
+ * Labels (nearest).  nx = floor(sx + 0.5), ny = floor(sy + 0.5) in fp64 (halves round up); the output is labels[ny][nx][c] for every
+ * channel c, an int32 copied as it is: no value ever passes through a float, so negatives, -1 and 2^31 - 1 come out unchanged.
+ *
+ * Image (bilinear).  x0 = floor(sx), lx = (float) (sx - x0) (the difference is exact in fp64, one rounding to fp32), hx = 1.0f - lx;
+ * likewise y0, ly, hy.  Each of the four taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) is first mapped to fp32 by the
+ * sample's intensity transform T (below): t00, t01, t10, t11.  Then
+ *     out = (hy * (hx * t00 + lx * t01)) + (ly * (hx * t10 + lx * t11)),
+ * every operation rounded to fp32, no fma: the order in which the bilinear kernels of this library blend.  A tap of weight 0 still
+ * takes part (0 * t).
+ *
+ * Border: one mode per call, for taps and labels alike, applied per axis to the integer index.
+ *   CPN_AUGMENT_BORDER_CONSTANT: a tap or label whose row or column lies outside the source is image_fill (a finite fp32, in the
+ *   OUTPUT's units: it is not mapped by T) or label_fill.  Where all four taps of a pixel are outside, the output is image_fill
+ *   itself (rounded to bf16 for a bf16 output), not the blend of four fills, whose fp32 weights need not sum to 1.
+ *   CPN_AUGMENT_BORDER_REFLECT: reflect-101 indexing: p = 2 (n - 1), i <- i mod p (non-negative), i <- p - i where i >= n; n = 1: 0.
+ * Range safety: indices are tested and reduced in fp64 BEFORE any conversion to an integer, so no map, NaN and infinities
+ * included, forms an address outside the source.  An index further than 2^31 from the origin (or NaN) is outside the rule: it
+ * counts as outside under CONSTANT and reads index 0 under REFLECT.  (The Python layer refuses such maps.)
+ *
+ * Intensity.  T is per sample and channel.
+ *   CPN_AUGMENT_IMAGE_U8: a table of 256 fp32 entries, t = table[b][k][v].  Table-then-blend: a departure from albumentations, which
+ *   blends the uint8 image, rounds to uint8 and then applies its tables; here nothing is rounded to uint8 in between.  The caller
+ *   composes gamma, contrast, brightness, the scale to [0, 1] and the normalisation into the table in fp64 and rounds each entry
+ *   once.  The kernel keeps the tables of its sample in LDS (K x 1 KiB).
+ *   CPN_AUGMENT_IMAGE_F32: t = v * scale + offset with tables[b][k] = {scale, offset}, product and sum each rounded to fp32.
+ *
+ * Layouts.  image [B][H][W][K] (uint8 or fp32, channels-last as datasets hold images), labels [B][H][W][C] int32; image_out
+ * [B][K][h][w] contiguous, out_dtype 0 (fp32) or 1 (bf16: one rounding to nearest even at the end), the codes of "Trainable
+ * convolution"; labels_out [B][h][w][C] int32 contiguous.  All samples of a call share the source size.  Outputs must not overlap
+ * inputs.  No atomics and no reductions: every output element is written exactly once, bit-identical from run to run.
+ *
+ * The launch.  One launch covers the batch: a workgroup of 256 lanes per CPN_AUGMENT_TILE x CPN_AUGMENT_TILE output tile and sample;
+ * a lane computes four consecutive columns and writes each image plane with one 16-byte store (8 bytes for bf16) where w is a
+ * multiple of 4 and image_out is aligned to it, element by element otherwise (the same values); the labels of a tile are copied
+ * with one lane per (pixel, channel) in output order.
+ *   cpn_augment_warp: image or labels may be null (a labels-only or image-only call: K, tables, image_fill, the dtypes and image_out,
+ *   or C, label_fill and labels_out, are then not read).  CPN_E_INVALID: both null; B, H, W, h or w below 1; K outside 1 ... 4; C
+ *   outside 1 ... CPN_AUGMENT_MAX_CHANNELS; an unknown dtype or border code; a non-finite image_fill; a null maps, tables or
+ *   output of a part that is asked for; a pointer not aligned to its element (maps: 8 bytes).  CPN_E_UNSUPPORTED: 2^31 or more pixels
+ *   in a source or a destination, more than 65535 samples or tile rows.  The call validates before it reads a pointer.
+ * Known limits: no anti-aliasing when scaling down; affine maps only (no optical or elastic distortion, no blur, no noise);
+ * table-then-blend; one source size per call; the four taps of a pixel are gathered from global memory, not staged in LDS.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CPN_AUGMENT_TILE 32
+#define CPN_AUGMENT_MAX_CHANNELS 65535
+#define CPN_AUGMENT_IMAGE_U8 0
+#define CPN_AUGMENT_IMAGE_F32 1
+#define CPN_AUGMENT_BORDER_CONSTANT 0
+#define CPN_AUGMENT_BORDER_REFLECT 1
+int cpn_augment_warp(const void *image, int32_t image_dtype /* u8 | f32 */, const int32_t *labels, int64_t B, int64_t H, int64_t W,
+                     int32_t K, int32_t C, const double *maps /* [B][6], device */,
+                     const float *tables /* u8: [B][K][256]; f32: [B][K][2]; device */, int32_t border, float image_fill,
+                     int32_t label_fill, void *image_out, int32_t out_dtype /* f32 | bf16 */, int32_t *labels_out, int64_t h, int64_t w,
+                     void *stream);
+
 /* ---- Optimizer step -----------------------------------------------------------------------------------------
  * What celldetection_amd.optim (AdamW, clip_grad_norm_, grad_norm, step_info) runs on: the global L2 norm of a list of gradients,
  * the clip coefficient, the AdamW update and the in-place scaling of the gradients, each one multi-tensor launch
