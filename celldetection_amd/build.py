@@ -68,6 +68,9 @@ SOURCES = {
     # trainable ResNet stem (7x7 stride-2 conv on the padded 4-channel input: pack, forward, weight gradient) and max-pool with its
     # tap index and gather gradient (index arithmetic: csrc/pool_adjoint.h)
     'stem_train.hip': [],
+    # trainable image conv (the 3x3 stride-1 first conv of the U-Net encoders on the padded 4-channel image: pad, pack, forward,
+    # weight gradient)
+    'image_conv_train.hip': [],
     # the optimizer step (global gradient norm, clip, AdamW): fp64 sums in a fixed order and an fp32 update defined operation by
     # operation (partition and lane mapping: csrc/optim_chunks.h): no FMA contraction, correctly rounded division and square root
     'optim.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],

@@ -1,6 +1,6 @@
 """The in-place converts: each replaces the stock modules one family (or one block) runs by this library's drop-ins, which share
 the ``Parameter`` and buffer objects of what they replace, and says what it left and why.  One walker, ``_walk``, and one adopt,
-``_adopt``, serve all nine; the families' ``_*_why_not`` rules decide.  This module imports the families, never the reverse."""
+``_adopt``, serve all ten; the families' ``_*_why_not`` rules decide.  This module imports the families, never the reverse."""
 import torch
 
 from ._common import _pair
@@ -10,13 +10,14 @@ from .blocks import (Bottleneck, CPNCore, UNetDecoder, _block_why_not, _core_why
 from .cat_conv import CatConv2d
 from .conv import Conv2d, _why_not
 from .grouped import GroupedConv2d, StridedConv1x1, _grouped_why_not
+from .image_conv import ImageConv2d, _image_why_not, _is_image_business
 from .pool import MaxPool2d, _pool_why_not
 from .readout_tail import DropoutConv1x1, _tail_why_not
 from .resize import ResizedConv2d
 from .stem import StemConv2d, _is_stem_business, _stem_why_not
 
 # the convs of this library (ResizedConv2d is a Conv2d): what the per-module converts of convs skip
-_OUR_CONVS = (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d, StemConv2d)
+_OUR_CONVS = (Conv2d, DropoutConv1x1, GroupedConv2d, StridedConv1x1, CatConv2d, StemConv2d, ImageConv2d)
 
 
 def _adopt(cls, module, **attributes):
@@ -153,6 +154,17 @@ def convert_stem_conv2d_(module):
     replaced by one object in all of them.  Works before or after the other converts."""
     return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and _is_stem_business(m),
                  lambda conv, parent: _stem_why_not(conv), lambda conv: _adopt(StemConv2d, conv))
+
+
+def convert_image_conv2d_(module):
+    """Replaces every eligible plain ``torch.nn.Conv2d`` below ``module`` -- ``in_channels <= 4``, ``out_channels`` 32, 64 or 128,
+    3x3, stride 1, padding 1 with zeros, dilation 1, groups 1: the first conv of a U-Net encoder -- in place by an ``ImageConv2d``
+    that shares its ``Parameter`` objects (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left:
+    reason}).  ``left`` names every other 3x3 conv from at most 4 channels with the reason; the remaining convs are not its business.
+    ``module`` itself is not replaced when it is such a conv: it is reported as left.  A conv object that sits in several slots is
+    replaced by one object in all of them.  Works before or after the other converts."""
+    return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and _is_image_business(m),
+                 lambda conv, parent: _image_why_not(conv), lambda conv: _adopt(ImageConv2d, conv))
 
 
 def convert_maxpool2d_(module):

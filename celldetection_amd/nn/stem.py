@@ -11,7 +11,8 @@ nothing else; its backward is a gather in a fixed order (no atomics, no scatter)
 After ``convert_conv2d_``, ``convert_batchnorm2d_``, ``convert_grouped_conv2d_``, ``convert_bottleneck_``, ``convert_stem_conv2d_`` and
 ``convert_maxpool2d_``, in any order, an encoder runs without a stock operation.  Known limits: batch-norm statistics are not
 folded into the stem's epilogue; the pool is not fused into the norm's apply; the sum of the pool's gradient and a lateral's stays
-autograd's add; 7x7 / stride 2 only (not the 3x3 first conv of the ``U22`` encoders); ``cda.models.*`` stay inference-only.
+autograd's add; 7x7 / stride 2 only (the 3x3 stride-1 first conv of the ``U22`` encoders is ``image_conv2d``, nn/image_conv.py);
+``cda.models.*`` stay inference-only.
 """
 import torch
 

@@ -1368,7 +1368,8 @@ int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, v
  * Saved for backward: by stem_conv2d Xp alone (4 channels for the image's 3: a third more than the image in bf16, plus the border), by
  * max_pool2d the uint8 index alone.  Known limits: no input gradient of the stem; batch-norm statistics are not folded into the
  * stem's epilogue; the pool is not fused into the norm's apply; the weight gradient stages every pixel's 64 bytes of Xp on their
- * own (the overlap of neighbouring pixels is left to the caches); 7x7 / stride 2 only.
+ * own (the overlap of neighbouring pixels is left to the caches); 7x7 / stride 2 only (the 3x3 stride-1 first conv of the U-Net
+ * encoders is the "Trainable image conv" section below).
  * ---------------------------------------------------------------------------------------------------------- */
 int cpn_stem_train_pack(const void *weight, int32_t weight_dtype, int32_t cout, int32_t cin, void *packed, void *stream);
 int cpn_stem_train_forward(const void *xp, const void *packed, const float *bias, int32_t N, int32_t H, int32_t W, int32_t cout,
@@ -1382,6 +1383,69 @@ int cpn_maxpool2d_indexed(const void *x, int32_t dtype, int32_t N, int32_t H, in
                           int32_t pad, void *y, void *index, void *stream);
 int cpn_maxpool2d_backward(const void *dy, const void *index, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k,
                            int32_t stride, int32_t pad, void *dx, void *stream);
+
+/* ---- Trainable image conv -----------------------------------------------------------------------------------
+ * What celldetection_amd.nn.image_conv2d runs: the first module of the reference's UNetEncoder (models/unet.py:29-58; CpnU22,
+ * CpnSlimU22, CpnWideU22, U17, U12), Conv2d(C <= 4 -> 32 | 64 | 128, 3x3, stride 1, padding 1) on the image itself
+ * (csrc/image_conv_train.hip, csrc/mfma_frag.h, csrc/stem_mfma.h -- its swap-and-store only --, csrc/wgrad_slabs.h,
+ * csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
+ *
+ * The conv's input is the padded 4-channel tensor Xq, bf16 [N][H + 2][Wq = W + 3][4] with a zero border (one row and one column
+ * in front, one row and two columns behind) and zeros in the channels c >= C.  The output has the image's size H x W.  The 16
+ * values (kx 0..3, c 0..3) that output pixel (y, x) meets in filter row ky are the 32 contiguous bytes at Xq[n][y + ky][x]; every
+ * such read lies inside Xq, the last row of the last image included (it ends at Xq's last byte).  Arithmetic: operands are rounded
+ * to bf16 (round to nearest even), sums are fp32, every stored value is rounded once.  Image values must be finite: the column
+ * kx = 3 multiplies a real neighbouring pixel (x + 2 of the image, where it exists) by a zero weight, as the stem's kx = 7 does,
+ * and an infinity or a NaN there would reach the sum.
+ *
+ *   cpn_image_conv_pad: src fp32 NCHW [N][C][H][W] -> Xq.  Round to nearest even, fp32 subnormals included (NaN stays NaN); what
+ *   cpn_convert_input_stem with range_flag = NULL does for the stem's border.  1 <= C <= 4.
+ *
+ *   cpn_image_conv_pack: weight [cout][cin][3][3] (weight_dtype 0 = fp32 | 1 = bf16) -> packed [3][cout][16] bf16: filter row,
+ *   output channel, (kx 0..3, c 0..3), zeros at kx = 3 and c >= cin.  Round to nearest even, fp32 subnormals included; bf16 weights
+ *   are copied.  Runs on the device every step.  cout 32 | 64 | 128, 1 <= cin <= 4 (CPN_E_INVALID).
+ *
+ *   cpn_image_conv_forward: y[n][y][x][co] = sum over (ky, kx, c) of Xq[n][y + ky][x + kx][c] * packed[ky][co][kx][c] (+ bias[co],
+ *   fp32, may be NULL), bf16 NHWC [N][H][W][cout], no activation.  A wave owns a fragment of 32 consecutive pixels of one image row
+ *   at a time (persistent waves, grid-stride over the N * H * ceil(W / 32) fragments, at most 4 | 3 | 2 workgroups of four waves
+ *   per CU for cout 32 | 64 | 128) and every output channel of it: one v_mfma_f32_32x32x16_bf16 step per filter row, so 3 steps per output in one fp32 accumulator, + 2
+ *   for the MFMA-internal sum, + the bias add, one rounding to bf16.  Both operands come straight from global memory (the weights
+ *   once per wave, the next fragment's pixels before this fragment's products); a lane stores 16 bytes = 8 consecutive channels of
+ *   its pixel.  Lanes behind a row's end recompute its last pixel and store nothing.
+ *
+ *   cpn_image_conv_wgrad: dw[co][c][ky][kx] = sum over (n, y, x) of dY[n][y][x][co] * Xq[n][y + ky][x + kx][c] for kx < 3 and
+ *   c < cin; dY bf16 NHWC [N][H][W][cout].  The reduction index is the flat output pixel p = (n H + y) W + x.  Slabs of slab_rows
+ *   image rows of the N * H rows (0 = auto: at most 512 slabs of equal size; csrc/wgrad_slabs.h); inside a slab the pixels in
+ *   ascending order, 16 per MFMA step, in ONE fp32 accumulator per element (no cross-wave sum).  A workgroup of four waves owns a
+ *   slab and all three filter rows.  Per chunk of 128 pixels it stages the dY rows in LDS once for all three filter rows, next to
+ *   two images of the pixels' Xq values: image 0 holds the 32 bytes of filter rows 0 and 1 side by side, image 1 those of filter row
+ *   2 and zeros.  Wave w owns image w % 2 and the 32-channel blocks w / 2 and w / 2 + 2 of dY, from the slab's first pixel to its
+ *   last (with cout = 32 waves 2 and 3 stage only); the next chunk's global loads are issued before this chunk's products.  Pixels
+ *   behind a slab's end are zeros in both operands.  The slabs' partial sums, workspace [slab][3][cout][16] fp32, are added in
+ *   ascending slab order (+ one add per slab) and rounded once to dw_dtype; the columns kx = 3 and c >= cin are never read, so they
+ *   never reach dw.  db[co] = the sum of dY, by the bias kernels of cpn_conv_wgrad: 8 interleaved chains per slab added in order,
+ *   then the slabs in ascending slab order.  No floating-point atomics: bit-identical from run to run.  There is no input gradient.
+ *   cpn_image_conv_wgrad_info: info[5] = {slabs, slab_rows, MFMA steps of the largest slab, reduce chain, bias chain}, what it means
+ *   for the stem; the chain of one dw element is info[2] + 2 + info[3].  cpn_image_conv_wgrad_workspace_bytes = slabs *
+ *   (3 * cout * 16 + cout) * 4.  Both answer without a GPU.
+ *   CPN_E_INVALID: N, H, W < 1, cout not 32 | 64 | 128, C or cin outside 1 ... 4, slab_rows < 0, a null or unaligned (16 bytes; src
+ *   of the pad: 4) pointer, dw and db both null, an unknown dtype code.  CPN_E_UNSUPPORTED: more than 2^31 - 1 pixels in Xq.
+ *   CPN_E_WORKSPACE: a workspace smaller than cpn_image_conv_wgrad_workspace_bytes.  Every call validates before it reads a pointer.
+ *
+ * Saved for backward by image_conv2d: Xq alone (8 bytes per pixel, plus the border).  Known limits: no input gradient; the 1x1
+ * shortcut and the ResBlock of ResUNet are not run; the norm's statistics are not folded into the epilogue; the conv's output is
+ * saved by the norm behind it, not recomputed in the norm's backward; no fp8; the forward's stores are 32 contiguous bytes per
+ * pixel and instruction (a pixel's line is completed by consecutive instructions of one wave).
+ * ---------------------------------------------------------------------------------------------------------- */
+int cpn_image_conv_pad(const float *src, int32_t N, int32_t C, int32_t H, int32_t W, void *xq, void *stream);
+int cpn_image_conv_pack(const void *weight, int32_t weight_dtype, int32_t cout, int32_t cin, void *packed, void *stream);
+int cpn_image_conv_forward(const void *xq, const void *packed, const float *bias, int32_t N, int32_t H, int32_t W, int32_t cout,
+                           void *y, void *stream);
+int cpn_image_conv_wgrad_info(int32_t N, int32_t H, int32_t W, int32_t cout, int32_t slab_rows, int32_t info[5]);
+int64_t cpn_image_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t cout, int32_t slab_rows);
+int cpn_image_conv_wgrad(const void *xq, const void *dy, int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                         int32_t slab_rows /* 0 = auto */, void *dw, int32_t dw_dtype, void *db, int32_t db_dtype, void *workspace,
+                         int64_t workspace_bytes, void *stream);
 
 /* ---- Trainable bilinear resize ------------------------------------------------------------------------------
  * What celldetection_amd.nn.bilinear_resize and nn.resized_conv2d need besides cpn_resize_bilinear, cpn_resize_bilinear_f32,
