@@ -65,11 +65,13 @@ SOURCES = {
     # weight gradient of a conv over the virtual resized tensor; the blend and the sums are defined by their order of operations
     # (index arithmetic: csrc/bilinear_adjoint.h): no FMA contraction
     'bilinear_train.hip': ['-ffp-contract=off'],
-    # trainable ResNet stem (7x7 stride-2 conv on the padded 4-channel input: pack, forward, weight gradient) and max-pool with its
-    # tap index and gather gradient (index arithmetic: csrc/pool_adjoint.h)
+    # trainable ResNet stem (7x7 stride-2 conv on the padded 4-channel input: forward, weight gradient; what it shares with the image
+    # conv: csrc/image_train.h)
     'stem_train.hip': [],
-    # trainable image conv (the 3x3 stride-1 first conv of the U-Net encoders on the padded 4-channel image: pad, pack, forward,
-    # weight gradient)
+    # max-pool with its tap index and gather gradient (index arithmetic: csrc/pool_adjoint.h)
+    'pool_train.hip': [],
+    # trainable image conv (the 3x3 stride-1 first conv of the U-Net encoders on the padded 4-channel image: pad, forward, weight
+    # gradient; pack, slab reduce, checks and host path: csrc/image_train.h)
     'image_conv_train.hip': [],
     # the optimizer step (global gradient norm, clip, AdamW): fp64 sums in a fixed order and an fp32 update defined operation by
     # operation (partition and lane mapping: csrc/optim_chunks.h): no FMA contraction, correctly rounded division and square root
@@ -85,7 +87,7 @@ SOURCES = {
     'conv_args.hip': [],
     'cpn_abi.hip': [],
 }
-HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'optim_chunks.h', 'warp_rule.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
+HEADERS = ['cpn_kernels.h', 'cpn_error.h', 'cpn_plan.h', 'lds_dma.h', 'polygon_fill.h', 'contour_trace.h', 'components.h', 'component_rank.h', 'wgrad_slabs.h', 'wgrad_bias.h', 'wgrad_dense.h', 'mfma_frag.h', 'stem_mfma.h', 'image_train.h', 'grouped_conv.h', 'nearest_adjoint.h', 'bilinear_adjoint.h', 'pool_adjoint.h', 'bn_slabs.h', 'tail_slabs.h', 'optim_chunks.h', 'warp_rule.h', 'efd_chunks.h', 'label_table.h', 'props_table.h', 'hull_count.h', 'decode_device.h', 'conv_igemm.hip', os.path.join('..', '..', 'include', 'cpn_hip.h')]
 
 
 def _hipcc():

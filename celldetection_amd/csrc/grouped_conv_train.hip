@@ -243,12 +243,7 @@ int cpn_grouped_conv_wgrad(const void *x, const void *dz, const void *dy, int32_
         hipLaunchKernelGGL(gc_wgrad_reduce_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, ws, c.part.slabs, c.geo, dw,
                            dw_dtype);
     }
-    if (db) {
-        hipLaunchKernelGGL(ct_bias_slab_kernel, dim3((unsigned) c.bpart.slabs, (unsigned) (C / 32)), dim3(256), 0, st,
-                           (const uint16_t *) dy, wsb, c.bpart, C);
-        hipLaunchKernelGGL(ct_bias_reduce_kernel, dim3((unsigned) ((C + 255) / 256)), dim3(256), 0, st, wsb, c.bpart.slabs, C, db,
-                           db_dtype);
-    }
+    if (db) ct_launch_bias(c.bpart, dy, wsb, C, db, db_dtype, st);
     return cpn::check_hip(hipGetLastError(), "cpn_grouped_conv_wgrad");
 }
 

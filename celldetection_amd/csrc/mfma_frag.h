@@ -4,7 +4,7 @@
 // address of ITS row, not of its column: of the 16 rows of a step the rows t = 8 (l / 32) + (l >> 2) % 4 and t + 4, at the byte
 // offset mf_lane_bytes of four columns, and the two reads together are the lane's operand.  D: lane l holds column j = l % 32,
 // register r holds row i = mf_row(r, l / 32).
-// Used by csrc/wgrad_dense.h, csrc/grouped_conv_train.hip, csrc/stem_train.hip (and csrc/stem_mfma.h) and csrc/readout_tail.hip.
+// Used by csrc/wgrad_dense.h, csrc/grouped_conv_train.hip, csrc/stem_train.hip, csrc/image_conv_train.hip (and csrc/stem_mfma.h) and csrc/readout_tail.hip.
 // Device code with internal linkage: every unit that includes this header gets its own copy, compiled with that unit's flags.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// Index arithmetic of the max-pool and of its gradient as a gather (csrc/stem_train.hip).  A pool of kernel k, stride s and padding
+// Index arithmetic of the max-pool and of its gradient as a gather (csrc/pool_train.hip).  A pool of kernel k, stride s and padding
 // pad (pad < k, s >= 1) maps `in` pixels of an axis to out = (in + 2 pad - k) / s + 1 windows; window o covers the positions
 // o * s - pad + t for the taps t = 0 ... k - 1, of which those in [0, in) exist (the window is CUT at the border, not clamped).
 // The forward stores per output element the tap index ty * k + tx of the position that gave the maximum; the backward lets every

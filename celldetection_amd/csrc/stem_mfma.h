@@ -8,12 +8,15 @@
 // v0 / v1: the sums + bias of channels j * 32 + 8 q + 4 lhi + e of the lane's pixel, q = 2 qp and 2 qp + 1 (lhi = lane / 32).  ch:
 // the first of the 8 consecutive channels the lane owns once the lane halves have swapped the quads they do not keep,
 // j * 32 + 8 (2 qp + lhi).  pixel: the flat output pixel; ok: false in the lanes behind the row's end, which store nothing.  The
-// epilogue applies its activation, converts, swaps and stores; stem_store_bf16 is the swap and the store of the bf16 layouts.
+// epilogue applies its activation, converts, swaps and stores; stem_store_bf16 is the swap and the store of the bf16 layouts and
+// StBf16 the epilogue without an activation, which the trainable image conv (csrc/image_conv_train.hip) stores through as well: its
+// loop prefetches and is its own.
 // Device code with internal linkage: every unit that includes this header gets its own copy, compiled with that unit's flags.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "mfma_frag.h"
+#include "wgrad_bias.h"  // ct_bf16_rne
 
 namespace {
 
@@ -30,6 +33,20 @@ __device__ __forceinline__ void stem_store_bf16(unsigned char *at, bool ok, unsi
     o.x = s0.x; o.y = s1.x; o.z = s0.y; o.w = s1.y;
     if (ok) *(u32x4 *) at = o;
 }
+
+__device__ __forceinline__ unsigned int stem_pack2(float lo, float hi) {
+    return (unsigned int) ct_bf16_rne(lo) | ((unsigned int) ct_bf16_rne(hi) << 16);
+}
+
+// the Epilogue of the trainable convs: no activation, bf16 by ct_bf16_rne, one 16-byte store
+struct StBf16 {
+    unsigned char *dst;
+    size_t stride;  // bytes per output pixel
+    __device__ __forceinline__ void operator()(const float (&v0)[4], const float (&v1)[4], int ch, size_t pixel, bool ok) const {
+        stem_store_bf16(dst + pixel * stride + (size_t) ch * 2, ok, stem_pack2(v0[0], v0[1]), stem_pack2(v0[2], v0[3]),
+                        stem_pack2(v1[0], v1[1]), stem_pack2(v1[2], v1[3]));
+    }
+};
 
 // NF = 32-channel output fragments (1 | 2); weights [7][NF * 32][32] bf16.  One wave = one 32-pixel row fragment at a time
 // (persistent waves, grid-stride: this one is wave `wave` of `nwaves`, which the kernel works out itself -- there the compiler

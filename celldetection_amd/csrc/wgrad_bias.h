@@ -1,6 +1,6 @@
 // The bias gradient of the trainable convs and the bf16 rounding they share (csrc/wgrad_dense.h, csrc/grouped_conv_train.hip):
 //   ct_bias_slab_kernel / ct_bias_reduce_kernel: sum of dY per channel, eight interleaved chains per slab added in order, then the
-//   slabs in ascending order.  No floating-point atomics.  The partition is csrc/wgrad_slabs.h.
+//   slabs in ascending order; ct_launch_bias launches the two.  No floating-point atomics.  The partition is csrc/wgrad_slabs.h.
 // Device code with internal linkage: every unit that includes this header gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,6 +45,13 @@ __global__ __launch_bounds__(256) void ct_bias_reduce_kernel(const float *__rest
     for (int s = 1; s < slabs; ++s) sum += wsb[(int64_t) s * Cout + ch];
     if (db_dtype == CT_BF16) ((uint16_t *) db)[ch] = ct_bf16_rne(sum);
     else ((float *) db)[ch] = sum;
+}
+
+// db [cout] from dY [pixel][cout] over the partition `part`: the slabs' sums into wsb [slab][cout], then the slabs in ascending order
+inline void ct_launch_bias(const WgSlabs &part, const void *dy, float *wsb, int cout, void *db, int db_dtype, hipStream_t st) {
+    hipLaunchKernelGGL(ct_bias_slab_kernel, dim3((unsigned) part.slabs, (unsigned) (cout / 32)), dim3(256), 0, st, (const uint16_t *) dy,
+                       wsb, part, cout);
+    hipLaunchKernelGGL(ct_bias_reduce_kernel, dim3((unsigned) ((cout + 255) / 256)), dim3(256), 0, st, wsb, part.slabs, cout, db, db_dtype);
 }
 
 }  // namespace

@@ -30,7 +30,7 @@
 #include "../../include/cpn_hip.h"  // the error codes
 #include "cpn_error.h"
 #include "mfma_frag.h"
-#include "wgrad_bias.h"  // ct_bias_slab_kernel / ct_bias_reduce_kernel, ct_bf16_rne, the dtype codes
+#include "wgrad_bias.h"  // ct_launch_bias, ct_bf16_rne, the dtype codes
 #include "wgrad_slabs.h"
 
 namespace {
@@ -296,12 +296,7 @@ void ct_launch_wgrad(const WgSlabs &part, const void *dy, const Source &src, int
         hipLaunchKernelGGL(ct_wgrad_reduce_kernel, dim3((unsigned) ((per + 255) / 256)), dim3(256), 0, st, ws, part.slabs, k * k, cout,
                            cin, dw, dw_dtype);
     }
-    if (db) {
-        hipLaunchKernelGGL(ct_bias_slab_kernel, dim3((unsigned) part.slabs, (unsigned) (cout / 32)), dim3(256), 0, st,
-                           (const uint16_t *) dy, wsb, part, cout);
-        hipLaunchKernelGGL(ct_bias_reduce_kernel, dim3((unsigned) ((cout + 255) / 256)), dim3(256), 0, st, wsb, part.slabs, cout, db,
-                           db_dtype);
-    }
+    if (db) ct_launch_bias(part, dy, wsb, cout, db, db_dtype, st);
 }
 
 #endif  // WGRAD_SLAB_KERNEL_ONLY

@@ -135,14 +135,20 @@ def convert_readout_tail_(module):
                  why_not, lambda conv, p: _adopt(DropoutConv1x1, conv, p=float(p)), fuse)
 
 
+def _convert_plain_conv2d(module, business, why_not, cls):
+    """The walk of the converts whose candidate is a ``torch.nn.Conv2d`` that is none of this library's convs and that
+    ``business`` takes for theirs; each becomes a ``cls`` unless ``why_not`` names a reason."""
+    return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and business(m),
+                 lambda conv, parent: why_not(conv), lambda conv: _adopt(cls, conv))
+
+
 def convert_grouped_conv2d_(module):
     """Replaces every eligible plain ``torch.nn.Conv2d`` with ``groups > 1`` below ``module`` in place by a ``GroupedConv2d`` that
     shares its ``Parameter`` objects (optimisers and ``state_dict`` keys are unaffected) -> (names replaced, {name left: reason}).
     ``left`` names every other grouped conv with the reason; dense convs are not its business.  ``module`` itself is not replaced
     when it is such a conv: it is reported as left.  A conv object that sits in several slots is replaced by one object in all of
     them.  Works before or after the other converts."""
-    return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and m.groups > 1,
-                 lambda conv, parent: _grouped_why_not(conv), lambda conv: _adopt(GroupedConv2d, conv))
+    return _convert_plain_conv2d(module, lambda m: m.groups > 1, _grouped_why_not, GroupedConv2d)
 
 
 def convert_stem_conv2d_(module):
@@ -152,8 +158,7 @@ def convert_stem_conv2d_(module):
     from at most 4 channels and every other 7x7 conv of stride 2 with the reason; the remaining convs are not its business.
     ``module`` itself is not replaced when it is such a conv: it is reported as left.  A conv object that sits in several slots is
     replaced by one object in all of them.  Works before or after the other converts."""
-    return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and _is_stem_business(m),
-                 lambda conv, parent: _stem_why_not(conv), lambda conv: _adopt(StemConv2d, conv))
+    return _convert_plain_conv2d(module, _is_stem_business, _stem_why_not, StemConv2d)
 
 
 def convert_image_conv2d_(module):
@@ -163,8 +168,7 @@ def convert_image_conv2d_(module):
     reason}).  ``left`` names every other 3x3 conv from at most 4 channels with the reason; the remaining convs are not its business.
     ``module`` itself is not replaced when it is such a conv: it is reported as left.  A conv object that sits in several slots is
     replaced by one object in all of them.  Works before or after the other converts."""
-    return _walk(module, lambda m: isinstance(m, torch.nn.Conv2d) and not isinstance(m, _OUR_CONVS) and _is_image_business(m),
-                 lambda conv, parent: _image_why_not(conv), lambda conv: _adopt(ImageConv2d, conv))
+    return _convert_plain_conv2d(module, _is_image_business, _image_why_not, ImageConv2d)
 
 
 def convert_maxpool2d_(module):

@@ -1,5 +1,5 @@
 """The max-pool in front of ``layer1`` and of the U-Net encoders ("Trainable stem and max-pool" of include/cpn_hip.h,
-csrc/stem_train.hip, csrc/pool_adjoint.h; the family is described with the stem's, in stem.py): ``max_pool2d`` stores one ``uint8``
+csrc/pool_train.hip, csrc/pool_adjoint.h; the family is described with the stem's, in stem.py): ``max_pool2d`` stores one ``uint8``
 tap index per output element and saves nothing else; its backward is a gather in a fixed order (no atomics, no scatter)."""
 import torch
 

@@ -1314,8 +1314,8 @@ int cpn_nearest_sum(const void *t, int32_t N, int32_t H, int32_t W, int32_t C, v
 /* ---- Trainable stem and max-pool ----------------------------------------------------------------------------
  * What celldetection_amd.nn.stem_conv2d and nn.max_pool2d run: the first two modules of a ResNet / ResNeXt encoder,
  * Conv2d(C <= 4 -> 32 | 64, 7x7, stride 2, padding 3) and MaxPool2d(3, 2, 1), and the MaxPool2d(2, 2) of the U-Net encoders
- * (csrc/stem_train.hip, csrc/stem_mfma.h -- the forward loop, shared with csrc/stem.hip --, csrc/mfma_frag.h, csrc/pool_adjoint.h,
- * csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
+ * (csrc/stem_train.hip, csrc/image_train.h, csrc/stem_mfma.h -- the forward loop, shared with csrc/stem.hip --, csrc/mfma_frag.h,
+ * csrc/pool_train.hip, csrc/pool_adjoint.h, csrc/wgrad_slabs.h, csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
  *
  * The stem's input is the padded 4-channel tensor Xp, bf16 [N][H + 6][W + 8][4] with a zero border (3 rows / columns in front) and
  * zeros in the channels c >= C, as cpn_convert_input_stem writes it (range_flag = NULL: a training input need not lie in [0, 1]).
@@ -1387,7 +1387,7 @@ int cpn_maxpool2d_backward(const void *dy, const void *index, int32_t dtype, int
 /* ---- Trainable image conv -----------------------------------------------------------------------------------
  * What celldetection_amd.nn.image_conv2d runs: the first module of the reference's UNetEncoder (models/unet.py:29-58; CpnU22,
  * CpnSlimU22, CpnWideU22, U17, U12), Conv2d(C <= 4 -> 32 | 64 | 128, 3x3, stride 1, padding 1) on the image itself
- * (csrc/image_conv_train.hip, csrc/mfma_frag.h, csrc/stem_mfma.h -- its swap-and-store only --, csrc/wgrad_slabs.h,
+ * (csrc/image_conv_train.hip, csrc/image_train.h, csrc/mfma_frag.h, csrc/stem_mfma.h -- its epilogue only --, csrc/wgrad_slabs.h,
  * csrc/wgrad_bias.h).  Additions to ABI 22.  This text is the contract.
  *
  * The conv's input is the padded 4-channel tensor Xq, bf16 [N][H + 2][Wq = W + 3][4] with a zero border (one row and one column

@@ -1,4 +1,4 @@
-// csrc/pool_adjoint.h and the stem weight gradient's staging on the host (tests/test_stem.py builds this host program with
+// csrc/pool_adjoint.h (the index arithmetic of csrc/pool_train.hip) and the stem weight gradient's staging on the host (tests/test_stem.py builds this host program with
 // AddressSanitizer and UBSan and runs it).  For every 1 <= H, W <= 12 that holds a window, in both geometries (3, 2, 1) and
 // (2, 2, 0), against brute force over the windows:
 //   - the windows [pa_first, pa_last] x [pa_first, pa_last] a pixel reports are exactly the windows that contain it, at most
@@ -72,7 +72,7 @@ static int check_pool(int H, int W, int k, int s, int pad) {
     return 0;
 }
 
-// the staging of st_wgrad_slab_kernel (csrc/stem_train.hip): chunks of 128 flat output pixels, 64 bytes at Xp[n][2 oy + ky][2 ox]
+// the X staging of st_wgrad_slab_kernel (csrc/stem_train.hip; its dY staging is csrc/image_train.h): chunks of 128 flat output pixels, 64 bytes at Xp[n][2 oy + ky][2 ox]
 static int check_stem_staging(int N, int H, int W, int slab_rows) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Hp = H + 6, Wp = W + 8;
     const int64_t bytes = (int64_t) N * Hp * Wp * 8;

@@ -1,5 +1,5 @@
 """GPU tests of the trainable stem and max-pool (``cda.nn.stem_conv2d``, ``stem_weight_grad``, ``max_pool2d`` and the entry points
-behind them; csrc/stem_train.hip) against the fp64 statements of tests/stem_oracle.py.  The forward is judged by the rule of
+behind them; csrc/stem_train.hip, csrc/pool_train.hip) against the fp64 statements of tests/stem_oracle.py.  The forward is judged by the rule of
 tests/conv_bounds.py with the 14 MFMA steps the kernel runs, the weight and bias gradients by the chain ``stem_weight_grad_info``
 reports (which the test itself caps), the pool's forward bit for bit, its gradient by a chain of three adds.  No allowance counts,
 no fraction of bad elements.  Outputs and workspaces of the direct launches lie in guarded buffers."""

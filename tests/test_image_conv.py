@@ -192,9 +192,13 @@ def test_header_binding_and_build_list_agree():
     assert 'image_conv_train.hip' in build.SOURCES and build.SOURCES['image_conv_train.hip'] == []
     assert {'wgrad_slabs.h', 'wgrad_bias.h', 'mfma_frag.h', 'stem_mfma.h'} <= set(build.HEADERS)
     assert {'image_conv2d', 'ImageConv2d', 'convert_image_conv2d_', 'image_pack_weight', 'image_weight_grad', 'image_weight_grad_info'} <= set(nn.__all__)
-    src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'image_conv_train.hip')).read()
+    # the unit and the shared headers its text moved to: csrc/image_train.h and the bias launch of csrc/wgrad_bias.h
+    unit, family, bias = (open(os.path.join(ROOT, 'celldetection_amd', 'csrc', name)).read()
+                          for name in ('image_conv_train.hip', 'image_train.h', 'wgrad_bias.h'))
+    assert '#include "image_train.h"' in unit and '#include "wgrad_bias.h"' in family and 'image_train.h' in build.HEADERS
+    src = unit + family + bias
     assert 'atomic' not in src.replace('No floating-point atomics', '') and 'fmaxf' not in src
-    assert 'mfma_f32_32x32x16_bf16' in src and 'mf_operand(' in src and 'wgs_partition(' in src and 'ct_bias_slab_kernel' in src
+    assert 'mfma_f32_32x32x16_bf16' in unit and 'mf_operand(' in unit and 'wgs_partition(' in src and 'ct_bias_slab_kernel' in src
     for doc in ('README.md',):
         text = open(os.path.join(ROOT, doc)).read()
         assert 'image_conv2d' in text and 'convert_image_conv2d_' in text and 'Trainable image conv on the GPU' in text, doc

@@ -1,4 +1,4 @@
-"""CPU tests of the trainable stem and max-pool (celldetection_amd/nn/stem.py, nn/pool.py, csrc/stem_train.hip, csrc/pool_adjoint.h): the fp64
+"""CPU tests of the trainable stem and max-pool (celldetection_amd/nn/stem.py, nn/pool.py, csrc/stem_train.hip, csrc/pool_train.hip, csrc/pool_adjoint.h): the fp64
 statements of tests/stem_oracle.py against torch's own float64 results, the wrong rules the cases tell apart, the pool's index
 arithmetic and the stem's staging on the host under sanitizers, the host-side entry points, the Python surface and the two converts
 on stand-ins with the reference's layout.  Nothing here needs a GPU."""
@@ -237,11 +237,17 @@ def test_header_binding_and_exports_agree():
                    'raster order of (oy, ox)', 'gets an exact 0', 'No floating-point atomics', 'NaN is outside the contract',
                    'There is no input gradient'):
         assert phrase in flat_hdr, phrase
-    assert 'stem_train.hip' in build.SOURCES and 'pool_adjoint.h' in build.HEADERS
+    assert 'stem_train.hip' in build.SOURCES and 'pool_adjoint.h' in build.HEADERS and 'image_train.h' in build.HEADERS
+    assert build.SOURCES['pool_train.hip'] == build.SOURCES['stem_train.hip'] == []
     assert {'stem_conv2d', 'StemConv2d', 'convert_stem_conv2d_', 'stem_pack_weight', 'stem_weight_grad', 'stem_weight_grad_info',
             'max_pool2d', 'MaxPool2d', 'convert_maxpool2d_'} <= set(nn.__all__)
-    src = open(os.path.join(ROOT, 'celldetection_amd', 'csrc', 'stem_train.hip')).read()
-    assert 'atomic' not in src.replace('No floating-point atomics', '') and 'fmaxf' not in src
+    # the stem's unit, what it shares with the image conv (csrc/image_train.h, the bias launch of csrc/wgrad_bias.h) and the pool's unit
+    src, family, bias, pool = (open(os.path.join(ROOT, 'celldetection_amd', 'csrc', name)).read()
+                               for name in ('stem_train.hip', 'image_train.h', 'wgrad_bias.h', 'pool_train.hip'))
+    for text in (src, family, bias, pool):
+        assert 'atomic' not in text.replace('No floating-point atomics', '') and 'fmaxf' not in text
+    assert '#include "image_train.h"' in src and '#include "wgrad_bias.h"' in family and '#include "pool_adjoint.h"' in pool
+    assert 'cpn_maxpool2d_indexed(' in pool and 'cpn_maxpool2d_backward(' in pool and 'maxpool' not in src
     # the forward loop and its swap-and-store are csrc/stem_mfma.h (shared with csrc/stem.hip), the transposed read csrc/mfma_frag.h
     loop, frag = (open(os.path.join(ROOT, 'celldetection_amd', 'csrc', name)).read() for name in ('stem_mfma.h', 'mfma_frag.h'))
     assert '#include "stem_mfma.h"' in src and '#include "mfma_frag.h"' in src and {'stem_mfma.h', 'mfma_frag.h'} <= set(build.HEADERS)
